@@ -11,7 +11,15 @@ full contraction of the fixture network. value = executed metric flops
 (sum over path steps of (8*s-2)*o, contraction_cost.rs:26-32) / wall time,
 aggregated over all ranks.
 
+A plain run sets up, warms up, times --steps contractions and prints the
+headline JSON line. --full adds everything that takes runs of its own: the
+rqc24/syc49 secondary lines, the profiled pass behind the `roofline` leg,
+the host `cpu_baseline`, and (N>1) the partition fan-in mechanism line.
+--dump-outputs DIR writes the final tensor of the last timed step to
+DIR/result.npy (trailing axis = re, im; float64 for c128, float32 for c64).
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--fixture rqc36]
+                       [--full] [--dump-outputs DIR]
 Multi-GPU: launched via torch.distributed.run, one rank per GPU (RCCL).
 """
 
@@ -41,9 +49,18 @@ def parse_args():
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--fixture", default="rqc36")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary fixtures, the profiled "
+                        "roofline pass, the host cpu_baseline and (N>1) the "
+                        "fan-in mechanism line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's final tensor to "
+                        "DIR/result.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the host cpu_baseline leg")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the rqc24/syc49 secondary evidence lines")
+                   help="with --full: skip the rqc24/syc49 secondary "
+                        "evidence lines")
     p.add_argument("--trials", type=int, default=16,
                    help="random-greedy trials for the multi-GPU plan")
     return p.parse_args()
@@ -239,6 +256,29 @@ def emit(result):
     print(json.dumps(result), flush=True)
 
 
+DUMP_CAP_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(outdir, data):
+    """Write the final tensor (complex ndarray) as DIR/result.npy: real
+    view with a trailing (re, im) axis, float64 for c128 / float32 for c64.
+    Outputs above the 64 MB cap are reduced to a fixed seeded sample of
+    flat elements (same indices every run)."""
+    import numpy as np
+
+    data = np.ascontiguousarray(data)
+    real = np.float64 if data.dtype == np.complex128 else np.float32
+    out = data.view(real).reshape(data.shape + (2,))
+    if out.nbytes > DUMP_CAP_BYTES:
+        flat = out.reshape(-1, 2)
+        keep = DUMP_CAP_BYTES // (2 * out.itemsize)
+        idx = np.sort(np.random.default_rng(0).integers(
+            0, flat.shape[0], size=keep))
+        out = flat[idx]
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "result.npy"), out)
+
+
 # workload descriptions (BASELINE.json configs; path provenance is in the
 # fixture meta, surfaced under config.path_provenance)
 WORKLOADS = {
@@ -252,6 +292,9 @@ WORKLOADS = {
 
 
 def run_single(args, fixture=None, steps=None, warmup=None, secondary=False):
+    """One fixture on one GPU. Plain: one untimed pass (arms hipGraph
+    capture), warmup, the timed steps. --full additionally profiles that
+    first pass for the roofline leg and times the host cpu_baseline."""
     from tnc_amd.contraction_path import ContractionPath
     from tnc_amd.executor import ContractionEngine
     from tnc_amd.fixtures import load_fixture
@@ -265,10 +308,16 @@ def run_single(args, fixture=None, steps=None, warmup=None, secondary=False):
     eng = ContractionEngine(tn, replace, device=0, dtype=dtype)
     flops_per_contraction = eng.total_flops
 
-    # one profiled pass (doubles as extra warmup)
-    _, step_ms, gemm_ms, kinds = eng.contract_profiled()
-    roofline = roofline_from_profile(eng.infos, step_ms, gemm_ms, kinds, dtype,
-                                     fixture)
+    roofline = None
+    if args.full:
+        # one profiled pass (doubles as extra warmup)
+        _, step_ms, gemm_ms, kinds = eng.contract_profiled()
+        roofline = roofline_from_profile(eng.infos, step_ms, gemm_ms, kinds,
+                                         dtype, fixture)
+    else:
+        # same pass unprofiled: arms graph capture, so the timed steps see
+        # the engine in the state the profiled pass would leave it in
+        eng.contract()
 
     for _ in range(warmup):
         eng.contract()
@@ -279,9 +328,11 @@ def run_single(args, fixture=None, steps=None, warmup=None, secondary=False):
 
     value = flops_per_contraction * steps / wall / 1e9
     infos = eng.infos
+    if args.dump_outputs and not secondary:
+        dump_outputs(args.dump_outputs, eng.result()[1])
     eng.close()  # release the device arena before the host-BLAS baseline
     cb = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         if dtype == "c128":
             # reference protocol: full-network oracle contraction (falls
             # back to the sampled estimate when host RAM is short)
@@ -393,6 +444,7 @@ def run_distributed(args):
     """
     import math as _math
 
+    import numpy as np
     import torch
     import torch.distributed as dist_t
 
@@ -428,7 +480,7 @@ def run_distributed(args):
     # shape, communication.rs:199-249) measured beside the slicing
     # headline so an 8-GPU run records both. Fail-safe: any error here
     # only drops this line, never the headline.
-    if not os.environ.get("TN_NO_FANIN"):
+    if args.full and not os.environ.get("TN_NO_FANIN"):
         try:
             _fanin_secondary(args, tn, frozen_path, meta, rank, world,
                              dev_id, device, backend, dist_t, torch,
@@ -459,10 +511,10 @@ def run_distributed(args):
     executed_flops = (sum(e.total_flops for e in engines[:1]) *
                       len(assignments)) if engines else 0.0
 
-    # rank 0's dominant-kernel roofline (one profiled pass, untimed; also
-    # extra warmup) so N>1 lines carry the roofline axis
+    # --full: rank 0's dominant-kernel roofline (one profiled pass, untimed;
+    # also extra warmup) so N>1 lines carry the roofline axis
     roofline = None
-    if rank == 0 and engines:
+    if args.full and rank == 0 and engines:
         _, p_step_ms, p_gemm_ms, p_kinds = engines[0].contract_profiled()
         roofline = roofline_from_profile(
             engines[0].infos, p_step_ms, p_gemm_ms, p_kinds, dtype,
@@ -502,6 +554,10 @@ def run_distributed(args):
             times.append(dt_t.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            npc = np.complex128 if dtype == "c128" else np.complex64
+            dump_outputs(args.dump_outputs,
+                         local.cpu().numpy().view(npc).reshape(-1))
         wall = sum(times)
         value = useful_flops * args.steps / wall / 1e9
         emit({
@@ -547,11 +603,11 @@ def main():
     if world > 1:
         run_distributed(args)
         return
-    # Secondary lines for the other BASELINE configs (rqc24 = config 2,
+    # --full: secondary lines for the other BASELINE configs (rqc24 = config 2,
     # syc49 = config 5/c64), emitted BEFORE the headline so the headline is
     # the last JSON line on stdout. Few steps each — they are evidence
     # lines, not the headline measurement.
-    if args.fixture == "rqc36" and not args.no_secondary:
+    if args.full and args.fixture == "rqc36" and not args.no_secondary:
         run_single(args, fixture="rqc24", steps=min(args.steps, 10),
                    warmup=min(args.warmup, 2), secondary=True)
         run_single(args, fixture="syc49", steps=min(args.steps, 5),

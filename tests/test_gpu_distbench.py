@@ -30,7 +30,8 @@ def test_distributed_bench_two_ranks_one_gpu():
         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
         "--master-port", "29551", os.path.join(ROOT, "bench.py"),
         "--gpus", "2", "--steps", "2", "--warmup", "1",
-        "--fixture", "rqc24", "--no-secondary", "--no-cpu-baseline",
+        "--fixture", "rqc24", "--full", "--no-secondary",
+        "--no-cpu-baseline",
     ]
     proc = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True,
                           text=True, timeout=420)
