@@ -1,10 +1,13 @@
 // zgemm variant tuning harness: times templated variants of the c128 MFMA
 // GEMM on a given (M, N, K), checks each against the baseline.
-// Usage: zgemm_tune [M N K]
+// Usage: zgemm_tune [M N K [all]]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <algorithm>
+#include <chrono>
+#include <cstring>
 #include <vector>
 
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -289,6 +292,113 @@ static void launch_glds_db(const double2* A, const double2* B, double2* C,
                      A, B, C, M, N, K, ct);
 }
 
+// glds + Gauss 3-multiply (3M): same LDS-DMA staging and swizzled image as
+// zg_glds, but three accumulator sets P1 = ArBr, P2 = AiBi,
+// P3 = (Ar+Ai)(Br+Bi) -> 3 MFMAs per complex MAC instead of 4; Cr = P1-P2,
+// Ci = P3-P1-P2 in the epilogue. WM x WN waves, each owning FM x FN 16x16
+// fragments; TN = WN*FN*16 must be 64 (the B swizzle assumes it). WPE pins
+// waves/SIMD (amdgpu_waves_per_eu) so the compiler neither takes the
+// register slack nor spills for occupancy it cannot use.
+template <int WM, int WN, int FM, int FN, int WPE>
+__global__ __launch_bounds__(WM * WN * 64)
+__attribute__((amdgpu_waves_per_eu(WPE, WPE))) void zg_glds_3m(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles) {
+  constexpr int NW = WM * WN, NT = NW * 64;
+  constexpr int TM = WM * FM * 16, TN = WN * FN * 16, KT = 16;
+  static_assert(TN == 64, "B swizzle assumes 64-column tiles");
+  static_assert((TM * KT) % NT == 0 && (KT * TN) % NT == 0, "staging split");
+  __shared__ double2 As[TM * KT];  // [r][c ^ (r & 15)]
+  __shared__ double2 Bs[KT * TN];  // [k][j ^ ((k & 3) << 4)]
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  const int wm = wave / WN, wn = wave % WN;
+  const unsigned tile = blockIdx.x;
+  const u64 brow = (u64)(tile / col_tiles) * TM;
+  const u64 bcol = (u64)(tile % col_tiles) * TN;
+  v4d p1[FM][FN], p2[FM][FN], p3[FM][FN];
+  for (int i = 0; i < FM; ++i)
+    for (int j = 0; j < FN; ++j) {
+      p1[i][j] = v4d{0, 0, 0, 0};
+      p2[i][j] = v4d{0, 0, 0, 0};
+      p3[i][j] = v4d{0, 0, 0, 0};
+    }
+  const int fi = lane % 16;
+  const int fk = lane / 16;
+  for (u64 k0 = 0; k0 < K; k0 += KT) {
+    for (int piece = 0; piece < TM * KT / NT; ++piece) {
+      int base = (wave * (TM * KT / NT) + piece) * 64;
+      int i = base + lane;
+      int r = i / KT, c_sw = i % KT;
+      int c = c_sw ^ (r & 15);
+      // wave-uniform 64-bit base + 32-bit lane offset (saddr form): the
+      // launcher guarantees TM*K*16 and KT*N*16 fit 32 bits
+      const char* src = (const char*)(A + brow * K + k0) +
+                        (unsigned)(((unsigned)r * (unsigned)K + c) * 16u);
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)&As[base], 16, 0, 0);
+    }
+    for (int piece = 0; piece < KT * TN / NT; ++piece) {
+      int base = piece * NT + wave * 64;
+      int j = base + lane;
+      int k = j / TN, col_sw = j % TN;
+      int col = col_sw ^ ((k & 3) << 4);
+      const char* src = (const char*)(B + k0 * N + bcol) +
+                        (unsigned)(((unsigned)k * (unsigned)N + col) * 16u);
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)&Bs[base], 16, 0, 0);
+    }
+    __syncthreads();  // carries vmcnt(0): drains the DMAs
+    for (int kq = 0; kq < KT / 4; ++kq) {
+      const int ak = kq * 4 + fk;
+      double2 a[FM], b[FN];
+      double as[FM], bs[FN];
+      for (int i = 0; i < FM; ++i) {
+        const int arow = (wm * FM + i) * 16 + fi;
+        a[i] = As[arow * KT + (ak ^ (arow & 15))];
+        as[i] = a[i].x + a[i].y;
+      }
+      for (int j = 0; j < FN; ++j) {
+        const int bcolf = (wn * FN + j) * 16 + fi;
+        b[j] = Bs[ak * TN + (bcolf ^ ((ak & 3) << 4))];
+        bs[j] = b[j].x + b[j].y;
+      }
+      for (int i = 0; i < FM; ++i)
+        for (int j = 0; j < FN; ++j) {
+          p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, p1[i][j], 0, 0, 0);
+          p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, p2[i][j], 0, 0, 0);
+          p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], p3[i][j], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+  }
+  const int ccol = lane % 16;
+  for (int i = 0; i < FM; ++i)
+    for (int j = 0; j < FN; ++j)
+      for (int r = 0; r < 4; ++r) {
+        u64 row = brow + (wm * FM + i) * 16 + (lane / 16) + 4 * r;
+        u64 col = bcol + (wn * FN + j) * 16 + ccol;
+        C[row * N + col] = make_double2(
+            p1[i][j][r] - p2[i][j][r],
+            (p3[i][j][r] - p1[i][j][r]) - p2[i][j][r]);
+      }
+}
+
+// pure shapes only (M % TM == 0, N % 64 == 0, K % 16 == 0): no guards
+template <int WM, int WN, int FM, int FN, int WPE>
+static void launch_3m(const double2* A, const double2* B, double2* C, u64 M,
+                      u64 N, u64 K) {
+  constexpr int TM = WM * FM * 16;
+  if (M % TM || N % 64 || K % 16) return;
+  if ((u64)TM * K * 16 > 0xffffffffull || 16 * N * 16 > 0xffffffffull) return;
+  u64 rt = M / TM, ct = N / 64;
+  hipLaunchKernelGGL((zg_glds_3m<WM, WN, FM, FN, WPE>),
+                     dim3((unsigned)(rt * ct)), dim3(WM * WN * 64), 0, 0, A, B,
+                     C, M, N, K, (unsigned)ct);
+}
+
 struct Variant {
   const char* name;
   void (*launch)(const double2*, const double2*, double2*, u64, u64, u64);
@@ -311,10 +421,13 @@ int main(int argc, char** argv) {
   u64 K = argc > 3 ? atoll(argv[3]) : 8192;
   std::vector<double2> hA(1), hB(1);
   double2 *A, *B, *C, *Cref;
-  (void)hipMalloc(&A, M * K * 16);
-  (void)hipMalloc(&B, K * N * 16);
-  (void)hipMalloc(&C, M * N * 16);
-  (void)hipMalloc(&Cref, M * N * 16);
+  if (hipMalloc(&A, M * K * 16) != hipSuccess ||
+      hipMalloc(&B, K * N * 16) != hipSuccess ||
+      hipMalloc(&C, M * N * 16) != hipSuccess ||
+      hipMalloc(&Cref, M * N * 16) != hipSuccess) {
+    fprintf(stderr, "hipMalloc failed\n");
+    return 1;
+  }
   // fill with pseudo-random device-side pattern via a tiny kernel
   auto fill = [](double2* p, u64 n, int seed) {
     struct L {
@@ -343,43 +456,69 @@ int main(int argc, char** argv) {
   fill(B, K * N, 2);
   (void)hipDeviceSynchronize();
 
-  Variant variants[] = {
-      {"w8 k16 (base)", launch_zg<8, 16, 0>},
-      {"w8 k16 glds", launch_glds},
-      {"w8 k16 glds-db", launch_glds_db},
+  // arms: the shipped glds 4M kernel is the reference; "all" as a 4th
+  // argument adds the older planar / double-buffered arms
+  const bool all = argc > 4 && !strcmp(argv[4], "all");
+  std::vector<Variant> variants = {
+      {"glds 4M (ref)", launch_glds},
+      {"3M-A 2x2w 128x64 e2", launch_3m<2, 2, 4, 2, 2>},
+      {"3M-B 2x2w 64x64 e3", launch_3m<2, 2, 2, 2, 3>},
+      {"3M-C 8x1w 128x64 e3", launch_3m<8, 1, 1, 4, 3>},
+      {"3M-D 4x2w 128x64 e3", launch_3m<4, 2, 2, 2, 3>},
+      {"3M-E 4x2w 256x64 e2", launch_3m<4, 2, 4, 2, 2>},
   };
-  double flops = 8.0 * M * N * K;
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  bool first = true;
-  for (auto& v : variants) {
-    v.launch(A, B, first ? Cref : C, M, N, K);  // warm + reference
+  if (all) {
+    variants.push_back({"w8 k16 planar", launch_zg<8, 16, 0>});
+    variants.push_back({"w8 k16 planar 3M", launch_zg<8, 16, 2>});
+    variants.push_back({"w8 k16 glds-db", launch_glds_db});
+  }
+  const double flops = 8.0 * M * N * K;  // metric flops (4M count)
+  const size_t nv = variants.size();
+  // warm every arm once, size its repeat count so a timed sample is >= 10 ms
+  // of back-to-back dispatches, and check it against the reference arm
+  std::vector<int> reps(nv, 1);
+  std::vector<double> err(nv, 0.0);
+  std::vector<std::vector<double>> ms(nv);
+  auto wall = [&](const Variant& v, double2* out, int n) {
     (void)hipDeviceSynchronize();
-    float best = 1e30f;
-    for (int rep = 0; rep < 3; ++rep) {
-      (void)hipEventRecord(e0);
-      v.launch(A, B, first ? Cref : C, M, N, K);
-      (void)hipEventRecord(e1);
-      (void)hipEventSynchronize(e1);
-      float ms;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      if (ms < best) best = ms;
-    }
-    double tf = flops / (best / 1e3) / 1e12;
-    double err = 0.0;
-    if (!first) {
-      // device-side compare (sampled): copy a strip
-      u64 sample = M * N > (u64)1 << 22 ? (u64)1 << 22 : M * N;
-      std::vector<double2> g(sample), r(sample);
-      (void)hipMemcpy(g.data(), C, sample * 16, hipMemcpyDeviceToHost);
+    auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < n; ++i) v.launch(A, B, out, M, N, K);
+    (void)hipDeviceSynchronize();
+    auto t1 = std::chrono::steady_clock::now();
+    return std::chrono::duration<double, std::milli>(t1 - t0).count() / n;
+  };
+  const u64 sample = M * N > (u64)1 << 22 ? (u64)1 << 22 : M * N;
+  std::vector<double2> g(sample), r(sample);
+  for (size_t i = 0; i < nv; ++i) {
+    double2* out = i == 0 ? Cref : C;
+    if (i) (void)hipMemset(C, 0xff, sample * 16);  // NaNs if an arm skips
+    wall(variants[i], out, 1);
+    double t = wall(variants[i], out, 1);
+    reps[i] = t >= 10.0 ? 1 : (int)ceil(10.0 / t);
+    if (i == 0) {
       (void)hipMemcpy(r.data(), Cref, sample * 16, hipMemcpyDeviceToHost);
-      for (u64 i = 0; i < sample; ++i)
-        err = fmax(err, fabs(g[i].x - r[i].x) + fabs(g[i].y - r[i].y));
+    } else {
+      (void)hipMemcpy(g.data(), C, sample * 16, hipMemcpyDeviceToHost);
+      for (u64 q = 0; q < sample; ++q) {
+        double d = fabs(g[q].x - r[q].x) + fabs(g[q].y - r[q].y);
+        if (!(d <= err[i])) err[i] = d == d ? d : INFINITY;
+      }
     }
-    printf("%-20s %8.3f ms  %7.2f TF/s  maxdiff_vs_v0=%.2e\n", v.name, best,
-           tf, err);
-    first = false;
+  }
+  // interleaved rounds: every arm once per round, unprofiled wall time
+  const int rounds = 5;
+  for (int rd = 0; rd < rounds; ++rd)
+    for (size_t i = 0; i < nv; ++i)
+      ms[i].push_back(wall(variants[i], i == 0 ? Cref : C, reps[i]));
+  printf("shape M=%llu N=%llu K=%llu  (wall ms per dispatch, %d interleaved "
+         "rounds)\n", M, N, K, rounds);
+  for (size_t i = 0; i < nv; ++i) {
+    std::sort(ms[i].begin(), ms[i].end());
+    double med = ms[i][rounds / 2];
+    printf("%-22s med %9.3f ms  min %9.3f  max %9.3f  x%-4d %7.2f TF/s(metric)"
+           "  vs_ref %.3f  maxdiff=%.2e\n",
+           variants[i].name, med, ms[i][0], ms[i][rounds - 1], reps[i],
+           flops / (med / 1e3) / 1e12, ms[0][rounds / 2] / med, err[i]);
   }
   return 0;
 }

@@ -525,7 +525,9 @@ __global__ __launch_bounds__(256) void k_zgemm_v1(
 // MFMA f64 kernel: v_mfma_f64_16x16x4_f64, 8 waves per block, 128x64 tile
 // (tile scan on the dominant rqc36 shape: 128x64/8-wave 58.7 TF/s vs
 // 64x64/4-wave 56.2; deeper K-tiles and 128-wide tiles lose to occupancy;
-// Gauss 3-mult loses to AGPR pressure — scripts/zgemm_tune.hip).
+// Gauss 3-mult lost on THIS planar-staged 8-wave layout, with no control of
+// the register budget — scripts/zgemm_tune.hip REORDER == 2; on the glds
+// staging with a 2x2-wave layout it wins, see k_zgemm_c128_glds_3m).
 // Wave w owns C rows [w*16, w*16+16); its row slab is 4 column fragments of
 // 16x16, each a {re, im} accumulator pair (4 f64 regs each). Per k-quad:
 // 4 MFMAs per fragment (Cr += ArBr; Cr += (-Ai)Bi; Ci += ArBi; Ci += AiBr).
@@ -823,6 +825,118 @@ __global__ __launch_bounds__(MF_THREADS) void k_zgemm_c128_glds_pure(
       u64 col = bcol + f * 16 + ccol;
       C[row * N + col] = make_double2(cr[f][r], ci[f][r]);
     }
+}
+
+
+// Gauss three-multiply (3M) variant of the pure-glds kernel: the GEMMs are
+// MFMA-pipe-bound, so the work left to remove is the MFMAs themselves.
+// Three accumulator sets P1 = Ar*Br, P2 = Ai*Bi, P3 = (Ar+Ai)*(Br+Bi) take 3
+// v_mfma_f64_16x16x4_f64 per complex MAC instead of 4; the epilogue forms
+// Cr = P1 - P2, Ci = (P3 - P1) - P2 (real-only operands give P3 == P1 and
+// P2 == 0 bit for bit, hence Ci == 0.0 exactly). Same 128x64x16 tile,
+// LDS-DMA staging, XOR-swizzled interleaved images, 32-bit tile decode and
+// D-fragment row map as k_zgemm_c128_glds_pure, so tile and split-K
+// arithmetic is unchanged. Layout: 4 waves as 2x2, each wave owns 64x32 =
+// 4x2 fragments (3 sets x 8 fragments x 8 regs = 192 accumulator VGPRs), the
+// operand sums a.x+a.y / b.x+b.y are formed once per k-quad in registers
+// (6 ds_read_b128 + 6 v_add_f64 per 24 MFMAs). waves_per_eu(2, 2) pins the
+// register budget at 256: launch_bounds alone lets the compiler take more,
+// asking for 3+ waves spills. Shipped build (kernel-resource-usage remarks):
+// 254 VGPRs, 0 AGPRs, no spill, 2 waves/SIMD, 48 KiB LDS -> 2 blocks/CU,
+// the same blocks/CU and tile traffic as the 4M kernel.
+// Staging addresses are a wave-uniform 64-bit base plus a 32-bit per-lane
+// byte offset (keeps the 12 DMA addresses out of the register budget): the
+// launcher must guarantee MF_T*K*16 and MF_K*N*16 fit in 32 bits, on top of
+// the pure-shape conditions (M % 128 == 0, N % 64 == 0, K-slices whole
+// 16-tiles). No guarded branch in the loop.
+#define MF3_THREADS 256
+__global__ __launch_bounds__(MF3_THREADS)
+__attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
+    unsigned tiles, u64 kchunk) {
+  constexpr int TM = MF_T, TN = MF_TN, KT = MF_K;
+  constexpr int WN = 2, FM = 4, FN = 2;
+  constexpr int APIECES = TM * KT / MF3_THREADS;  // 8 glds per wave
+  constexpr int BPIECES = KT * TN / MF3_THREADS;  // 4 glds per wave
+  __shared__ double2 As[TM * KT];  // [r][c ^ (r & 15)]
+  __shared__ double2 Bs[KT * TN];  // [k][j ^ ((k & 3) << 4)]
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  const int wm = wave / WN, wn = wave % WN;
+  const unsigned tile = (unsigned)blockIdx.x % tiles;
+  const unsigned slice = (unsigned)blockIdx.x / tiles;
+  const u64 brow = (u64)(tile / col_tiles) * TM;
+  const u64 bcol = (u64)(tile % col_tiles) * TN;
+  const u64 kbeg = (u64)slice * kchunk;
+  const u64 kend = (kbeg + kchunk < K) ? kbeg + kchunk : K;
+  C += (u64)slice * M * N;
+  v4d p1[FM][FN], p2[FM][FN], p3[FM][FN];
+  for (int i = 0; i < FM; ++i)
+    for (int j = 0; j < FN; ++j) {
+      p1[i][j] = v4d{0, 0, 0, 0};
+      p2[i][j] = v4d{0, 0, 0, 0};
+      p3[i][j] = v4d{0, 0, 0, 0};
+    }
+  const int fi = lane % 16;
+  const int fk = lane / 16;
+  for (u64 k0 = kbeg; k0 < kend; k0 += KT) {
+    for (int piece = 0; piece < APIECES; ++piece) {
+      int base = (wave * APIECES + piece) * 64;
+      int i = base + lane;
+      int r = i / KT, c_sw = i % KT;
+      int c = c_sw ^ (r & 15);
+      const char* src = (const char*)(A + brow * K + k0) +
+                        (unsigned)(((unsigned)r * (unsigned)K + c) * 16u);
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)&As[base], 16, 0, 0);
+    }
+    for (int piece = 0; piece < BPIECES; ++piece) {
+      int base = piece * MF3_THREADS + wave * 64;
+      int j = base + lane;
+      int k = j / TN, col_sw = j % TN;
+      int col = col_sw ^ ((k & 3) << 4);
+      const char* src = (const char*)(B + k0 * N + bcol) +
+                        (unsigned)(((unsigned)k * (unsigned)N + col) * 16u);
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)&Bs[base], 16, 0, 0);
+    }
+    __syncthreads();  // carries vmcnt(0): drains the LDS-DMAs
+    for (int kq = 0; kq < KT / 4; ++kq) {
+      const int ak = kq * 4 + fk;
+      double2 a[FM], b[FN];
+      double as[FM], bs[FN];
+      for (int i = 0; i < FM; ++i) {
+        const int arow = (wm * FM + i) * 16 + fi;
+        a[i] = As[arow * KT + (ak ^ (arow & 15))];
+        as[i] = a[i].x + a[i].y;
+      }
+      for (int j = 0; j < FN; ++j) {
+        const int bcolf = (wn * FN + j) * 16 + fi;
+        b[j] = Bs[ak * TN + (bcolf ^ ((ak & 3) << 4))];
+        bs[j] = b[j].x + b[j].y;
+      }
+      for (int i = 0; i < FM; ++i)
+        for (int j = 0; j < FN; ++j) {
+          p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, p1[i][j], 0, 0, 0);
+          p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, p2[i][j], 0, 0, 0);
+          p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], p3[i][j], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+  }
+  const int ccol = lane % 16;
+  for (int i = 0; i < FM; ++i)
+    for (int j = 0; j < FN; ++j)
+      for (int r = 0; r < 4; ++r) {
+        u64 row = brow + (wm * FM + i) * 16 + (lane / 16) + 4 * r;
+        u64 col = bcol + (wn * FN + j) * 16 + ccol;
+        C[row * N + col] = make_double2(
+            p1[i][j][r] - p2[i][j][r],
+            (p3[i][j][r] - p1[i][j][r]) - p2[i][j][r]);
+      }
 }
 
 
@@ -1382,6 +1496,41 @@ static bool gather_gemm_disabled() {
     v = (e && e[0] && e[0] != '0') ? 0 : 1;
   }
   return v == 1;
+}
+
+// Gauss 3M GEMM switch (TN_GEMM3M, read once at load): unset = use the 3M
+// kernel where the profitability gate admits the shape, "0" = never (the
+// same binary reproduces the 4M-only dispatch), "force" = wherever the
+// kernel's structural preconditions hold, gate ignored (tests; this also
+// lets split-K slices run through it, which the default never does).
+enum { GEMM3M_OFF = 0, GEMM3M_GATED = 1, GEMM3M_FORCE = 2 };
+static int gemm3m_mode() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("TN_GEMM3M");
+    if (!e || !e[0])
+      v = GEMM3M_GATED;
+    else if (!strcmp(e, "force"))
+      v = GEMM3M_FORCE;
+    else
+      v = (e[0] == '0') ? GEMM3M_OFF : GEMM3M_GATED;
+  }
+  return v;
+}
+
+// Structural preconditions of k_zgemm_c128_glds_3m beyond purity: its
+// staging offsets are 32-bit.
+static bool gemm3m_fits(u64 N, u64 K) {
+  return (u64)MF_T * K * 16 <= 0xffffffffull &&
+         (u64)MF_K * N * 16 <= 0xffffffffull;
+}
+
+// Profitability gate on (K, tile count), from the interleaved harness table
+// (profiles/r03_kernel_stats.md): 3M beat the 4M kernel by 1.16-1.27x on
+// every measured pure shape, K = 32..32768 and 256..131072 tiles. Nothing
+// smaller was measured, so nothing smaller is admitted.
+static bool gemm3m_profitable(u64 K, u64 tiles) {
+  return K >= 32 && tiles >= 256;
 }
 
 // Launch the best permute kernel for a gather described by `ax` (tiled
@@ -1976,12 +2125,24 @@ static int einsum_dev_impl(const u64* out_labels, const u64* out_shape,
     if constexpr (std::is_same_v<CT, double2>) {
       bool pure = (M % MF_T == 0) && (N % MF_TN == 0) && (K % MF_K == 0) &&
                   (kchunk % MF_K == 0);
+      // 3M routing: pure, unsplit, not a gather-GEMM step (pipeline windows
+      // returned above) and past the profitability gate; "force" drops the
+      // gate and the unsplit condition
+      const int m3 = gemm3m_mode();
+      const bool use_3m =
+          pure && !gather_gemm && m3 != GEMM3M_OFF && gemm3m_fits(N, K) &&
+          (m3 == GEMM3M_FORCE ||
+           (splitk == 1 && gemm3m_profitable(K, tiles)));
       // gather_gemm implies pure: its precondition covers M/N/K tiling and
       // kchunk is MF_K-rounded above
       if (gather_gemm)
         k_zgemm_c128_glds_gather<<<grid, MF_THREADS, 0, stream>>>(
             Adata, Bdata, gemm_out, M, N, K, (unsigned)col_tiles,
             (unsigned)tiles, kchunk, gmA, gmB);
+      else if (pure && use_3m)
+        k_zgemm_c128_glds_3m<<<grid, MF3_THREADS, 0, stream>>>(
+            Ag, Bg, gemm_out, M, N, K, (unsigned)col_tiles, (unsigned)tiles,
+            kchunk);
       else if (pure)
         k_zgemm_c128_glds_pure<<<grid, MF_THREADS, 0, stream>>>(
             Ag, Bg, gemm_out, M, N, K, (unsigned)col_tiles, (unsigned)tiles,
