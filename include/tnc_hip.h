@@ -88,6 +88,64 @@ int tn_einsum_c64_dev(const uint64_t* out_labels, const uint64_t* out_shape,
 /* Select the HIP device used by subsequently created nets / einsum calls. */
 int tn_set_device(int device);
 
+/* ------------------------- step planner ------------------------------ */
+
+enum { TN_ROUTE_DOT = 0, TN_ROUTE_GATHER = 1, TN_ROUTE_TTGT = 2 };
+enum { TN_DOT_LINEAR = 0, TN_DOT_TILED = 1, TN_DOT_GATHER = 2 };
+enum {
+  TN_GEMM_V1 = 0,          /* LDS-tiled VALU GEMM, ragged / small shapes */
+  TN_GEMM_MFMA = 1,        /* generic MFMA GEMM (c64 with ragged edges) */
+  TN_GEMM_C128_GLDS = 2,   /* c128 MFMA, ragged edges */
+  TN_GEMM_C128_PURE = 3,   /* c128 MFMA, M%128 == N%64 == K%16 == 0 */
+  TN_GEMM_C128_3M = 4,     /* c128 Gauss three-multiply MFMA */
+  TN_GEMM_C128_GATHER = 5, /* c128 MFMA reading through the pack permute */
+  TN_GEMM_C64_PURE = 6,    /* c64 MFMA, pure shapes */
+};
+
+/* How one einsum step is dispatched: everything that follows from dtype,
+ * shapes, strides and the TN_* environment switches alone. What depends on
+ * an allocation failing at run time (split-K dropping to 1, the pipeline
+ * dropping to the serial pack, out-of-memory dropping to the gather route)
+ * is not in here. */
+typedef struct tn_step_plan {
+  uint64_t m, n, k;
+  int32_t route;    /* TN_ROUTE_* */
+  int32_t kind;     /* as tn_net_contract_profiled reports it:
+                     * 0 gather, 1 dot, 5 linear dot, 6 tiled dot,
+                     * 2 TTGT, 3 TTGT with out permute */
+  int32_t dot_form; /* TN_DOT_* (dot route) */
+  int32_t tbits;    /* tiled dot: bits left to the grid */
+  uint64_t dot_blocks; /* dot route: partial-sum blocks */
+  int32_t gather_ok;   /* TTGT may drop to the gather route on out-of-memory */
+  int32_t pack_a, pack_b; /* operand is not already in [M][K] / [K][N] order
+                           * (reported on every route) */
+  int32_t direct;      /* GEMM writes `out` without a final permute */
+  int32_t gather_gemm; /* packs folded into the GEMM's staging */
+  /* pack pipeline: pipe_p K-windows of pipe_kc over the first pipe_npre K
+   * legs of A; 0 = serial pack */
+  int32_t pipe_p, pipe_npre;
+  uint64_t pipe_kc;
+  /* GEMM of the serial path */
+  uint64_t row_tiles, col_tiles, splitk, kchunk;
+  int32_t kernel; /* TN_GEMM_* */
+  /* workspace bytes the step will ask for. A pipelined step holds its window
+   * buffers in ws_pack_a / ws_pack_b and has no split buffer. */
+  uint64_t ws_pack_a, ws_pack_b, ws_tmp_c, ws_slices, ws_split, ws_dot;
+} tn_step_plan;
+
+/* Plan the step tn_einsum_*_dev would run on these operands (dtype 0 =
+ * complex128, 1 = complex64; has_stream2 = a second stream is available for
+ * the pack pipeline, as inside a tn_net). Needs no GPU and touches none.
+ * NULL strides mean contiguous row-major. Returns TN_ERR_INVALID, with the
+ * text in tn_last_error, for operands the einsum would reject. */
+int tn_plan_step(int dtype, const uint64_t* out_labels,
+                 const uint64_t* out_shape, size_t out_ndim,
+                 const uint64_t* a_labels, const uint64_t* a_shape,
+                 const int64_t* a_strides, size_t a_ndim,
+                 const uint64_t* b_labels, const uint64_t* b_shape,
+                 const int64_t* b_strides, size_t b_ndim, int has_stream2,
+                 tn_step_plan* plan);
+
 /* ------------ network executor (contract_tensor_network) ------------- */
 
 typedef struct tn_net tn_net;

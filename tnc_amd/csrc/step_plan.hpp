@@ -1,0 +1,505 @@
+// step_plan.hpp — the one place a contraction step's dispatch is decided.
+//
+// plan_step() maps (dtype, out order, operand shapes/strides, environment) to
+// a StepPlan: route (dot / gather / TTGT), which operands get packed, the
+// pack-pipeline windows, split-K, the GEMM kernel and the workspace the step
+// will ask for. No HIP call, no HIP header: it builds with a plain host
+// compiler and runs without a GPU. The executor (einsum_dev_impl), the
+// prepack look-ahead (plan_prepack) and the Python arena model (through
+// tn_plan_step) all read this plan; none re-derives it. Only what depends on
+// an allocation failing at run time stays in the executor: split-K falling
+// back to 1, the pipeline to the serial pack, out-of-memory to the gather
+// route.
+
+#ifndef TNC_STEP_PLAN_HPP
+#define TNC_STEP_PLAN_HPP
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/tnc_hip.h"
+
+typedef uint64_t u64;
+typedef int64_t i64;
+
+// ---- tile constants shared by the kernels and the planner -----------------
+
+#define TN_MAXR 40   // max axes per map
+#define TN_SMALLK 64 // LDS-precomputed K offsets
+
+// k_dot_tile: 6 a-bits (lane index) + 6 b-bits per block, the rest one block
+// per combination
+#define TN_DOT_TILE_ABITS 6
+#define TN_DOT_TILE_BBITS 6
+#define TN_DOT_TILE_BITS (TN_DOT_TILE_ABITS + TN_DOT_TILE_BBITS)
+#define TN_DOT_MAXBITS 34
+
+#define GT 64         // k_zgemm_v1 tile edge; column-tile width of every GEMM
+#define MF_T 128      // MFMA tile rows = MF_WAVES * 16
+#define MF_TN 64      // MFMA tile cols
+#define MF_K 16
+
+// ---- plain-data kernel arguments the planner fills ------------------------
+
+struct DotPerm {
+  int rbits;
+  u64 restA[TN_DOT_MAXBITS];  // element strides of each rest bit
+  u64 restB[TN_DOT_MAXBITS];
+  u64 bA[TN_DOT_TILE_BBITS];  // A strides of the b-bits
+  u64 bB[TN_DOT_TILE_BBITS];  // B strides of the b-bits (ascending)
+  u64 aB[TN_DOT_TILE_ABITS];  // B strides of the a-bits (A strides are 1<<i)
+};
+
+struct GatherGemmMap {
+  int rbits, kbits;   // bits of the row index (M for A / N for B) and of k
+  u64 rstride[34];    // source stride (elements) contributed by row bit b
+  u64 kstride[34];    // source stride contributed by k bit b
+};
+
+struct Meta {
+  int nd;
+  u64 labels[TN_MAXR];
+  u64 dims[TN_MAXR];
+  i64 strides[TN_MAXR];  // in elements
+  const void* data;
+};
+
+struct AxisInfo {
+  u64 dim;
+  i64 sa;
+  i64 sb;
+};
+
+// fixed-capacity axis list (a step plans without touching the heap)
+struct AxisList {
+  int n = 0;
+  int v[TN_MAXR];
+  void push_back(int x) { v[n++] = x; }
+  bool empty() const { return n == 0; }
+  int operator[](int i) const { return v[i]; }
+  int front() const { return v[0]; }
+  int back() const { return v[n - 1]; }
+  const int* begin() const { return v; }
+  const int* end() const { return v + n; }
+};
+
+// ---- environment switches, each read once on first use --------------------
+//   TN_NO_PIPELINE    set: never use the pack pipeline
+//   TN_PIPELINE_FORCE set: pipeline every shape-feasible step, profitability
+//                     gate ignored (tests: runs the window/event machinery
+//                     on small cases)
+//   TN_GATHER_GEMM    set: allow the gather-staged GEMM. OPT-IN: on the rqc36
+//                     dominant shapes it is ~35% SLOWER than pack + pure GEMM
+//                     (44.9 vs 69.6 TF/s on M16384/N4096/K32768), because the
+//                     GEMM re-reads its operand strips ~12x across tiles —
+//                     the pack is a bandwidth AMORTIZER, not removable
+//                     overhead. Kept for low-reuse shapes and as a recorded
+//                     negative result.
+//   TN_GEMM3M         unset: Gauss 3M kernel where the profitability gate
+//                     admits the shape; "0": never (the 4M-only dispatch);
+//                     "force": wherever the kernel's structural preconditions
+//                     hold, gate ignored (tests; also lets split-K slices
+//                     run through it, which the default never does)
+//   TN_NO_PREPACK     set: no look-ahead pack of the next step's operands
+enum EnvSwitch { ENV_NO_PIPELINE, ENV_PIPELINE_FORCE, ENV_GATHER_GEMM,
+                 ENV_GEMM3M, ENV_NO_PREPACK, ENV_COUNT };
+enum { GEMM3M_OFF = 0, GEMM3M_GATED = 1, GEMM3M_FORCE = 2 };
+
+inline int env_switch(EnvSwitch s) {
+  static const char* const names[ENV_COUNT] = {
+      "TN_NO_PIPELINE", "TN_PIPELINE_FORCE", "TN_GATHER_GEMM", "TN_GEMM3M",
+      "TN_NO_PREPACK"};
+  static int cache[ENV_COUNT] = {-1, -1, -1, -1, -1};
+  int& v = cache[s];
+  if (v < 0) {
+    const char* e = getenv(names[s]);
+    const bool on = e && e[0] && e[0] != '0';
+    if (s != ENV_GEMM3M)
+      v = on ? 1 : 0;
+    else if (!e || !e[0])
+      v = GEMM3M_GATED;
+    else
+      v = !strcmp(e, "force") ? GEMM3M_FORCE : on ? GEMM3M_GATED : GEMM3M_OFF;
+  }
+  return v;
+}
+
+// The plan: the exported scalars (tn_step_plan, include/tnc_hip.h) plus what
+// only the executor needs, the axis lists and the kernel-argument maps.
+struct StepPlan : tn_step_plan {
+  int apos[TN_MAXR], bpos[TN_MAXR];  // position in A / B of each out axis
+  AxisList m_out, n_out;             // positions (in out) of M legs / N legs
+  AxisList k_a, k_b;                 // K legs, A order: axes in A / in B
+  // GEMM operand layouts: A' = [M legs in out order][K legs in A order],
+  // B' = [K legs in A order][N legs in out order]
+  AxisList a_axes, b_axes;
+  DotPerm dp;              // dot route, tiled form
+  GatherGemmMap gmA{}, gmB{};  // TTGT route, gather_gemm
+  u64 nout() const { return m * n; }
+};
+
+inline int grid_for(u64 nout, int block = 256) {
+  u64 blocks = (nout + (u64)block - 1) / block;
+  u64 cap = 64 * 2048;  // grid-stride covers the remainder
+  if (blocks > cap) blocks = cap;
+  if (blocks == 0) blocks = 1;
+  return (int)blocks;
+}
+
+// Tiled bit-permutation dot: both operands are contiguous pow2 spans of the
+// same K elements in different axis orders. Fills *dp and returns the number
+// of rest bits (one block per combination), or -1 when the form does not
+// apply.
+inline int plan_dot_tile(const Meta& A, const Meta& B, const AxisList& k_a,
+                         const AxisList& k_b, DotPerm* dp) {
+  struct BitSB {
+    u64 sa, sb;
+  };
+  std::vector<BitSB> bits;
+  for (int t = 0; t < k_a.n; ++t) {
+    const u64 dim = A.dims[k_a[t]];
+    const i64 sa = A.strides[k_a[t]], sb = B.strides[k_b[t]];
+    if (dim == 1) continue;  // contributes no bits
+    if ((dim & (dim - 1)) || sa <= 0 || sb <= 0) return -1;
+    for (u64 d = 1; d < dim; d <<= 1)
+      bits.push_back({(u64)sa * d, (u64)sb * d});
+  }
+  const int bb = TN_DOT_TILE_BBITS;
+  const int nb = (int)bits.size();
+  if (nb > TN_DOT_MAXBITS || nb <= TN_DOT_TILE_ABITS + bb) return -1;
+  std::vector<int> byA(nb), byB(nb);
+  for (int i = 0; i < nb; ++i) byA[i] = byB[i] = i;
+  std::sort(byA.begin(), byA.end(),
+            [&](int x, int y) { return bits[x].sa < bits[y].sa; });
+  std::sort(byB.begin(), byB.end(),
+            [&](int x, int y) { return bits[x].sb < bits[y].sb; });
+  for (int i = 0; i < nb; ++i)
+    if (bits[byA[i]].sa != (1ull << i) || bits[byB[i]].sb != (1ull << i))
+      return -1;  // not a contiguous span on both sides
+  std::vector<char> used(nb, 0);
+  for (int i = 0; i < TN_DOT_TILE_ABITS; ++i) {
+    used[byA[i]] = 1;
+    dp->aB[i] = bits[byA[i]].sb;
+  }
+  int nbb = 0, nr = 0;
+  for (int i = 0; i < nb && nbb < bb; ++i) {
+    const int bi = byB[i];
+    if (used[bi]) continue;
+    dp->bA[nbb] = bits[bi].sa;
+    dp->bB[nbb] = bits[bi].sb;
+    used[bi] = 1;
+    ++nbb;
+  }
+  for (int i = 0; i < nb; ++i) {
+    if (used[byA[i]]) continue;
+    dp->restA[nr] = bits[byA[i]].sa;
+    dp->restB[nr] = bits[byA[i]].sb;
+    ++nr;
+  }
+  dp->rbits = nr;
+  return nr;
+}
+
+// Build the bit-scatter map of a packed [row][k] (or [k][col]) layout:
+// packed-index bit b -> source stride. Axes are outer..inner; the inner
+// axis supplies the low bits. Fails on non-pow2 dims or non-positive
+// strides (the step then takes the pack path).
+inline bool build_ggmap(const Meta& t, const int* axes_r, int nr,
+                        const int* axes_k, int nk, GatherGemmMap* m) {
+  auto fill = [&](const int* axes, int count, u64* stride, int* nbits) {
+    int nb = 0;
+    for (int x = count - 1; x >= 0; --x) {
+      u64 d = t.dims[axes[x]];
+      if (d & (d - 1)) return false;
+      if (d > 1 && t.strides[axes[x]] <= 0) return false;
+      for (u64 v = 1; v < d; v <<= 1) {
+        if (nb >= 34) return false;
+        stride[nb++] = (u64)t.strides[axes[x]] * v;
+      }
+    }
+    *nbits = nb;
+    return true;
+  };
+  return fill(axes_r, nr, m->rstride, &m->rbits) &&
+         fill(axes_k, nk, m->kstride, &m->kbits);
+}
+
+// Structural preconditions of k_zgemm_c128_glds_3m beyond purity: its
+// staging offsets are 32-bit.
+inline bool gemm3m_fits(u64 N, u64 K) {
+  return (u64)MF_T * K * 16 <= 0xffffffffull &&
+         (u64)MF_K * N * 16 <= 0xffffffffull;
+}
+
+// Profitability gate on (K, tile count), from the interleaved harness table
+// (profiles/r03_kernel_stats.md): 3M beat the 4M kernel by 1.16-1.27x on
+// every measured pure shape, K = 32..32768 and 256..131072 tiles. Nothing
+// smaller was measured, so nothing smaller is admitted.
+inline bool gemm3m_profitable(u64 K, u64 tiles) {
+  return K >= 32 && tiles >= 256;
+}
+
+// Pack-pipeline choice: chunk the pack over P K-windows (the first npre K
+// legs of A, kc = K / P each) so each window's permute overlaps the previous
+// window's GEMM. The window GEMMs write split-K-style slices reduced at the
+// end; the pack permutes (HBM-bound, ~4 TB/s) ride in the MFMA-bound GEMM's
+// spare bandwidth (slice traffic streams at ~6 TB/s). Chosen when the model
+// predicts a net win over the serial pack (the slice buffers cost (2p)·M·N
+// extra traffic). Requires a packed A (a ready A's K-windows are strided); B
+// may be packed or ready (row windows are contiguous).
+inline void plan_pipeline(StepPlan& p, const Meta& A, u64 esize) {
+  const u64 M = p.m, N = p.n, K = p.k;
+  u64 packbytes = ((p.pack_a ? M * K : 0) + (p.pack_b ? K * N : 0)) * esize;
+  struct Win {
+    int p = 0, npre = 0;
+    u64 kc = 0;
+  } best, feas;  // best by the model; last (= finest) feasible
+  double best_save = 0.0;
+  u64 w = 1;
+  u64 tiles_w = (M / MF_T) * ((N + MF_TN - 1) / MF_TN);
+  for (int x = 0; x < p.k_a.n && w < 16; ++x) {
+    w *= A.dims[p.k_a[x]];
+    if (w < 2 || w > 16) continue;
+    u64 kc = K / w;
+    if (kc % MF_K || tiles_w < 256) continue;
+    double save = 2.0 * (double)packbytes / 4e12 * (1.0 - 1.0 / w) -
+                  2.0 * w * (double)(M * N * esize) / 6e12;
+    feas = {(int)w, x + 1, kc};
+    if (save > best_save) {
+      best_save = save;
+      best = feas;
+    }
+  }
+  // measured gate (r02 A/B on hardware): marginal steps LOSE to the
+  // serial pack (window-launch overhead + slice-reduce traffic), so
+  // pipeline only when the predicted win is substantial and the pack
+  // dwarfs the output (rqc36's 4-10x-ratio steps regressed ~12 ms;
+  // syc49's 64x step gains ~12 ms)
+  if (env_switch(ENV_PIPELINE_FORCE) && feas.p)
+    best = feas;
+  else if (best_save <= 5e-3 ||
+           (double)packbytes < 8.0 * (double)(M * N * esize))
+    best.p = 0;
+  p.pipe_p = best.p;
+  p.pipe_kc = best.p ? best.kc : 0;
+  p.pipe_npre = best.p ? best.npre : 0;
+}
+
+// Plan one einsum step out = A · B (out contiguous row-major in out order).
+// Returns TN_OK, or TN_ERR_INVALID with the message in *err.
+inline int plan_step(bool c128, const u64* out_labels, const u64* out_shape,
+                     int out_nd, const Meta& A, const Meta& B,
+                     bool has_stream2, StepPlan* plan, std::string* err) {
+  StepPlan& p = *plan;
+  p = StepPlan();
+  const u64 esize = c128 ? 16 : 8;
+  auto fail = [&](const char* fmt, u64 v) {
+    char buf[128];
+    snprintf(buf, sizeof buf, fmt, (unsigned long long)v);
+    *err = buf;
+    return (int)TN_ERR_INVALID;
+  };
+  if (A.nd > TN_MAXR || B.nd > TN_MAXR || out_nd > TN_MAXR)
+    return fail("tensor rank exceeds %llu", TN_MAXR);
+  auto find = [](const Meta& t, u64 lab) {
+    for (int i = 0; i < t.nd; ++i)
+      if (t.labels[i] == lab) return i;
+    return -1;
+  };
+  int* apos = p.apos;
+  int* bpos = p.bpos;
+  u64 M = 1, N = 1, K = 1;
+  for (int i = 0; i < out_nd; ++i) {
+    apos[i] = find(A, out_labels[i]);
+    bpos[i] = find(B, out_labels[i]);
+    if (apos[i] >= 0 && bpos[i] >= 0)
+      return fail("out label %llu present in both inputs", out_labels[i]);
+    if (apos[i] >= 0) {
+      if (A.dims[apos[i]] != out_shape[i])
+        return fail("dim mismatch on out label %llu", out_labels[i]);
+      M *= out_shape[i];
+      p.m_out.push_back(i);
+    } else if (bpos[i] >= 0) {
+      if (B.dims[bpos[i]] != out_shape[i])
+        return fail("dim mismatch on out label %llu", out_labels[i]);
+      N *= out_shape[i];
+      p.n_out.push_back(i);
+    } else {
+      return fail("out label %llu not found in inputs", out_labels[i]);
+    }
+  }
+  for (int i = 0; i < A.nd; ++i) {
+    int j = find(B, A.labels[i]);
+    if (j >= 0) {
+      for (int o = 0; o < out_nd; ++o)
+        if (out_labels[o] == A.labels[i])
+          return fail("contracted label %llu appears in out", A.labels[i]);
+      if (A.dims[i] != B.dims[j])
+        return fail("K dim mismatch on label %llu", A.labels[i]);
+      K *= A.dims[i];
+      p.k_a.push_back(i);
+      p.k_b.push_back(j);
+    }
+  }
+  // every input label must be contracted (shared) or appear in out — traces
+  // and repeated labels are outside the tensor_mult boundary contract
+  // (contraction.rs:88-116 always passes the symmetric difference)
+  auto in_out = [&](u64 lab) {
+    for (int o = 0; o < out_nd; ++o)
+      if (out_labels[o] == lab) return true;
+    return false;
+  };
+  for (int i = 0; i < A.nd; ++i)
+    if (find(B, A.labels[i]) < 0 && !in_out(A.labels[i]))
+      return fail("label %llu of A neither contracted nor in out",
+                  A.labels[i]);
+  for (int i = 0; i < B.nd; ++i)
+    if (find(A, B.labels[i]) < 0 && !in_out(B.labels[i]))
+      return fail("label %llu of B neither contracted nor in out",
+                  B.labels[i]);
+  p.m = M;
+  p.n = N;
+  p.k = K;
+  const u64 nout = M * N;
+
+  // is each operand already contiguous in its GEMM layout? (reported for
+  // every route; only the TTGT route acts on it)
+  for (int o : p.m_out) p.a_axes.push_back(apos[o]);
+  for (int i : p.k_a) p.a_axes.push_back(i);
+  for (int j : p.k_b) p.b_axes.push_back(j);
+  for (int o : p.n_out) p.b_axes.push_back(bpos[o]);
+  auto is_ready = [](const Meta& t, const AxisList& axes) {
+    if (axes.n != t.nd) return false;
+    i64 stride = 1;
+    for (int i = axes.n - 1; i >= 0; --i) {
+      if (t.strides[axes[i]] != stride) return false;
+      stride *= (i64)t.dims[axes[i]];
+    }
+    return true;
+  };
+  p.pack_a = !is_ready(A, p.a_axes);
+  p.pack_b = !is_ready(B, p.b_axes);
+  // does the GEMM's C = [M..][N..] equal `out` directly? True iff the M
+  // legs all precede the N legs there (always so for the executor's
+  // symmetric-difference order)
+  p.direct = !(!p.m_out.empty() && !p.n_out.empty() &&
+               p.m_out.back() > p.n_out.front());
+
+  // ---- dot: scalar output, large K ----
+  if (M == 1 && N == 1 && K > TN_SMALLK) {
+    p.route = TN_ROUTE_DOT;
+    // linear iff each axis' source stride equals its packed suffix product
+    bool linear = true;
+    i64 pstride = 1;
+    for (int t = p.k_a.n - 1; t >= 0; --t) {
+      if (A.strides[p.k_a[t]] != pstride || B.strides[p.k_b[t]] != pstride)
+        linear = false;
+      pstride *= (i64)A.dims[p.k_a[t]];
+    }
+    int tbits = -1;
+    if (!linear && K >= (1ull << 20))
+      tbits = plan_dot_tile(A, B, p.k_a, p.k_b, &p.dp);
+    if (tbits > 0) {
+      p.dot_form = TN_DOT_TILED;
+      p.kind = 6;
+      p.tbits = tbits;
+      p.dot_blocks = 1ull << tbits;
+    } else {
+      p.dot_form = linear ? TN_DOT_LINEAR : TN_DOT_GATHER;
+      p.kind = linear ? 5 : 1;  // 5 = linear (streaming) dot
+      p.dot_blocks = (u64)std::min(grid_for(K), 2048);
+    }
+    p.ws_dot = p.dot_blocks * 16;  // double2 partials for either dtype
+    return TN_OK;
+  }
+
+  // ---- smallk / anyk: small K, or skinny GEMM shapes ----
+  // mid-K big shapes (e.g. M=2^20 N=2^10 K=32) run ~3x faster as a packed
+  // MFMA GEMM than as an address-gather stream
+  const bool skinny = (M < 16 || N < 16);
+  const bool gemm_worthy = (K >= 16 && M >= MF_T && N >= MF_TN);
+  p.gather_ok = (K <= TN_SMALLK || skinny);
+  if (p.gather_ok && !gemm_worthy) {
+    p.route = TN_ROUTE_GATHER;
+    p.kind = 0;
+    return TN_OK;
+  }
+
+  // ---- TTGT: pack (if needed) + GEMM + unpack (if needed) ----
+  p.route = TN_ROUTE_TTGT;
+  p.kind = p.direct ? 2 : 3;
+  const bool mfma_shape = (M >= 32 && N >= 32);
+  const bool pure_shape =
+      (M % MF_T == 0) && (N % MF_TN == 0) && (K % MF_K == 0);
+  // gather-staged GEMM (c128): fold the pack permutes into the GEMM's LDS
+  // staging when the shape is pure and every dim is pow2 — no pack
+  // kernels, no pack workspace, no pack HBM traffic
+  if (c128 && (p.pack_a || p.pack_b) && mfma_shape && pure_shape &&
+      env_switch(ENV_GATHER_GEMM))
+    p.gather_gemm =  // a_axes = [M.., K..], b_axes = [K.., N..]
+        build_ggmap(A, p.a_axes.v, p.m_out.n, p.k_a.v, p.k_a.n, &p.gmA) &&
+        build_ggmap(B, p.b_axes.v + p.k_b.n, p.n_out.n, p.k_b.v, p.k_b.n,
+                    &p.gmB);
+  if (has_stream2 && p.pack_a && mfma_shape && pure_shape &&
+      !env_switch(ENV_NO_PIPELINE))
+    plan_pipeline(p, A, esize);
+
+  // the GEMM of the serial path (also what a pipelined step runs when its
+  // window buffers cannot be had)
+  const u64 row_tile_h = mfma_shape ? MF_T : GT;
+  p.row_tiles = (M + row_tile_h - 1) / row_tile_h;
+  p.col_tiles = (N + GT - 1) / GT;
+  const u64 tiles = p.row_tiles * p.col_tiles;
+  // split-K: with few tiles and deep K, slice K across extra blocks into
+  // partial buffers + a reduce pass (fills the 256 CUs; a 64-tile K=2^20
+  // GEMM goes from ~6 to ~50 TFLOP/s)
+  u64 splitk = 1;
+  if (tiles < 192 && K >= 256) {
+    while (tiles * splitk < 256 && K / (splitk * 2) >= 64) splitk *= 2;
+    if (splitk > 64) splitk = 64;
+  }
+  u64 kchunk = (K + splitk - 1) / splitk;
+  kchunk = ((kchunk + MF_K - 1) / MF_K) * MF_K;  // tile-aligned
+  p.kchunk = kchunk;
+  p.splitk = (K + kchunk - 1) / kchunk;
+  // The kernel does not depend on whether the split buffer is obtained:
+  // the gated 3M route needs >= 256 tiles and split-K fewer than 192, and
+  // the forced one ignores splitk.
+  const bool pure = pure_shape && (kchunk % MF_K == 0);
+  if (!mfma_shape) {
+    p.kernel = TN_GEMM_V1;
+  } else if (!c128) {
+    p.kernel = pure ? TN_GEMM_C64_PURE : TN_GEMM_MFMA;
+  } else if (p.gather_gemm) {
+    // gather_gemm implies pure: its precondition covers M/N/K tiling and
+    // kchunk is MF_K-rounded above
+    p.kernel = TN_GEMM_C128_GATHER;
+  } else {
+    // 3M routing: pure, unsplit and past the profitability gate; "force"
+    // drops the gate and the unsplit condition
+    const int m3 = env_switch(ENV_GEMM3M);
+    const bool use_3m =
+        pure && m3 != GEMM3M_OFF && gemm3m_fits(N, K) &&
+        (m3 == GEMM3M_FORCE ||
+         (p.splitk == 1 && gemm3m_profitable(K, tiles)));
+    p.kernel = use_3m ? TN_GEMM_C128_3M
+                      : pure ? TN_GEMM_C128_PURE : TN_GEMM_C128_GLDS;
+  }
+
+  // workspace the step will ask for (a pipelined step's pack buffers hold
+  // all P windows back to back)
+  const bool packs = p.pipe_p || !p.gather_gemm;
+  p.ws_tmp_c = p.direct ? 0 : nout * esize;
+  p.ws_pack_a = (packs && p.pack_a) ? M * K * esize : 0;
+  p.ws_pack_b = (packs && p.pack_b) ? K * N * esize : 0;
+  p.ws_slices = (u64)p.pipe_p * nout * esize;
+  p.ws_split = (!p.pipe_p && p.splitk > 1) ? p.splitk * nout * esize : 0;
+  return TN_OK;
+}
+
+#endif  // TNC_STEP_PLAN_HPP

@@ -32,9 +32,7 @@
 #include <vector>
 
 #include "../../include/tnc_hip.h"
-
-typedef uint64_t u64;
-typedef int64_t i64;
+#include "step_plan.hpp"
 
 // ---------------------------------------------------------------------------
 // error plumbing
@@ -63,9 +61,6 @@ extern "C" const char* tn_last_error(void) { return g_last_error.c_str(); }
 // ---------------------------------------------------------------------------
 // gather maps
 // ---------------------------------------------------------------------------
-
-#define TN_MAXR 40   // max axes per map
-#define TN_SMALLK 64 // LDS-precomputed K offsets
 
 struct GatherMap {
   int n;
@@ -316,19 +311,7 @@ __global__ void k_dot_partial_linear(const CT* __restrict__ A,
 // block's loads overlap another's compute; the 128x64 variant measured
 // 10.7 ms vs 6.2 ms for this at K=2^30 c128; XOR-swizzled so both the
 // b-major writes and a-major reads are bank-conflict-free), then streams A.
-#define TN_DOT_TILE_ABITS 6
-#define TN_DOT_TILE_BBITS 6
-#define TN_DOT_TILE_BITS (TN_DOT_TILE_ABITS + TN_DOT_TILE_BBITS)
-#define TN_DOT_MAXBITS 34
-
-struct DotPerm {
-  int rbits;
-  u64 restA[TN_DOT_MAXBITS];  // element strides of each rest bit
-  u64 restB[TN_DOT_MAXBITS];
-  u64 bA[TN_DOT_TILE_BBITS];  // A strides of the b-bits
-  u64 bB[TN_DOT_TILE_BBITS];  // B strides of the b-bits (ascending)
-  u64 aB[TN_DOT_TILE_ABITS];  // B strides of the a-bits (A strides are 1<<i)
-};
+// (TN_DOT_TILE_* and DotPerm: step_plan.hpp)
 
 template <typename CT, int BB>
 __global__ __launch_bounds__(512) void k_dot_tile(const CT* __restrict__ A,
@@ -466,8 +449,7 @@ __global__ void k_permute_ct(const CT* __restrict__ src,
 // 64x64 C tile per 256-thread block; linearized grid (tile = blockIdx.x,
 // row tile = tile / col_tiles) so huge M or N never overflow grid dims.
 
-#define GT 64
-#define GK 16
+#define GK 16  // (GT: step_plan.hpp)
 
 template <typename CT>
 __global__ __launch_bounds__(256) void k_zgemm_v1(
@@ -561,9 +543,7 @@ struct MfmaCore<float> {
   }
 };
 
-#define MF_T 128      // tile rows = MF_WAVES * 16
-#define MF_TN 64      // tile cols
-#define MF_K 16
+// (MF_T x MF_TN tile, MF_K deep: step_plan.hpp)
 #define MF_THREADS 512
 #define A_LD 17  // padded row stride (elements) for the A tiles
 #define B_LD 66  // padded row stride for the B tiles
@@ -950,13 +930,7 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m(
 // heavier than the multiply it replaces. Everything else (XOR-swizzled
 // interleaved LDS image, MFMA body, epilogue) is identical to
 // k_zgemm_c128_glds_pure. Launched only for pure shapes (M%128 == 0,
-// N%64 == 0, K%16 == 0) with all-pow2 dims.
-struct GatherGemmMap {
-  int rbits, kbits;   // bits of the row index (M for A / N for B) and of k
-  u64 rstride[34];    // source stride (elements) contributed by row bit b
-  u64 kstride[34];    // source stride contributed by k bit b
-};
-
+// N%64 == 0, K%16 == 0) with all-pow2 dims. (GatherGemmMap: step_plan.hpp)
 __global__ __launch_bounds__(MF_THREADS) void k_zgemm_c128_glds_gather(
     const double2* __restrict__ A, const double2* __restrict__ B,
     double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
@@ -1160,20 +1134,6 @@ __global__ void k_splitk_reduce(const CT* __restrict__ ws,
 // host-side planning
 // ---------------------------------------------------------------------------
 
-struct Meta {
-  int nd;
-  u64 labels[TN_MAXR];
-  u64 dims[TN_MAXR];
-  i64 strides[TN_MAXR];  // in elements
-  const void* data;
-};
-
-struct AxisInfo {
-  u64 dim;
-  i64 sa;
-  i64 sb;
-};
-
 static int log2_u64(u64 v) {
   int s = 0;
   while ((1ull << s) < v) ++s;
@@ -1366,14 +1326,6 @@ static void ws_free(WsCtx& ctx, void* p) {
   (void)hipFree(p);  // hipFree device-syncs before releasing the pages
 }
 
-static int grid_for(u64 nout, int block = 256) {
-  u64 blocks = (nout + (u64)block - 1) / block;
-  u64 cap = 64 * 2048;  // grid-stride covers the remainder
-  if (blocks > cap) blocks = cap;
-  if (blocks == 0) blocks = 1;
-  return (int)blocks;
-}
-
 // Launch the tiled permute when the axis list describes a pow2 full-span
 // bit permutation (contiguous source, >= 2^20 elements); returns false to
 // fall back to the gather permute (strided views, non-pow2, tiny sizes).
@@ -1437,102 +1389,6 @@ static bool permute_tiled(const CT* src, CT* dst, u64 elems,
   return true;
 }
 
-// Build the bit-scatter map of a packed [row][k] (or [k][col]) layout:
-// packed-index bit b -> source stride. Axes are outer..inner; the inner
-// axis supplies the low bits. Fails on non-pow2 dims or non-positive
-// strides (the gather GEMM then falls back to the pack path).
-static bool build_ggmap(const Meta& t, const std::vector<int>& axes_r,
-                        const std::vector<int>& axes_k, GatherGemmMap* m) {
-  auto fill = [&](const std::vector<int>& axes, u64* stride, int* nbits) {
-    int nb = 0;
-    for (int x = (int)axes.size() - 1; x >= 0; --x) {
-      u64 d = t.dims[axes[x]];
-      if (d & (d - 1)) return false;
-      if (d > 1 && t.strides[axes[x]] <= 0) return false;
-      for (u64 v = 1; v < d; v <<= 1) {
-        if (nb >= 34) return false;
-        stride[nb++] = (u64)t.strides[axes[x]] * v;
-      }
-    }
-    *nbits = nb;
-    return true;
-  };
-  return fill(axes_r, m->rstride, &m->rbits) &&
-         fill(axes_k, m->kstride, &m->kbits);
-}
-
-static bool pipeline_disabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("TN_NO_PIPELINE");
-    v = (e && e[0] && e[0] != '0') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-// testing hook: run every shape-feasible step through the pipeline,
-// ignoring the profitability gate (exercises the window/event machinery
-// on small cases the gate would reject)
-static bool pipeline_forced() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("TN_PIPELINE_FORCE");
-    v = (e && e[0] && e[0] != '0') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-// The gather-staged GEMM is OPT-IN (TN_GATHER_GEMM=1): measured on the
-// rqc36 dominant shapes it is ~35% SLOWER than pack + pure GEMM (44.9 vs
-// 69.6 TF/s on M16384/N4096/K32768) because the GEMM re-reads its operand
-// strips ~12x across tiles — the pack is a bandwidth AMORTIZER (scattered
-// source read once, packed copy re-read coalesced), not removable
-// overhead. Kept for low-reuse shapes and as a recorded negative result
-// (DESIGN.md "Round-2 measured state").
-static bool gather_gemm_disabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("TN_GATHER_GEMM");
-    v = (e && e[0] && e[0] != '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-// Gauss 3M GEMM switch (TN_GEMM3M, read once at load): unset = use the 3M
-// kernel where the profitability gate admits the shape, "0" = never (the
-// same binary reproduces the 4M-only dispatch), "force" = wherever the
-// kernel's structural preconditions hold, gate ignored (tests; this also
-// lets split-K slices run through it, which the default never does).
-enum { GEMM3M_OFF = 0, GEMM3M_GATED = 1, GEMM3M_FORCE = 2 };
-static int gemm3m_mode() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("TN_GEMM3M");
-    if (!e || !e[0])
-      v = GEMM3M_GATED;
-    else if (!strcmp(e, "force"))
-      v = GEMM3M_FORCE;
-    else
-      v = (e[0] == '0') ? GEMM3M_OFF : GEMM3M_GATED;
-  }
-  return v;
-}
-
-// Structural preconditions of k_zgemm_c128_glds_3m beyond purity: its
-// staging offsets are 32-bit.
-static bool gemm3m_fits(u64 N, u64 K) {
-  return (u64)MF_T * K * 16 <= 0xffffffffull &&
-         (u64)MF_K * N * 16 <= 0xffffffffull;
-}
-
-// Profitability gate on (K, tile count), from the interleaved harness table
-// (profiles/r03_kernel_stats.md): 3M beat the 4M kernel by 1.16-1.27x on
-// every measured pure shape, K = 32..32768 and 256..131072 tiles. Nothing
-// smaller was measured, so nothing smaller is admitted.
-static bool gemm3m_profitable(u64 K, u64 tiles) {
-  return K >= 32 && tiles >= 256;
-}
-
 // Launch the best permute kernel for a gather described by `ax` (tiled
 // bit-permutation when applicable, else the index-gather permute).
 template <typename CT>
@@ -1552,655 +1408,395 @@ static int launch_permute(const CT* src, CT* dst, u64 elems,
   return TN_OK;
 }
 
+// ---------------------------------------------------------------------------
 // core einsum over device buffers; out is contiguous row-major in out order.
+// plan_step (step_plan.hpp) decides everything that follows from shapes,
+// strides, dtype and environment; the route functions below only allocate,
+// launch and release.
+// ---------------------------------------------------------------------------
+
+// one planned step, as the route functions see it
 template <typename CT>
-static int einsum_dev_impl(const u64* out_labels, const u64* out_shape,
-                           int out_nd, const Meta& A, const Meta& B,
-                           CT* out, hipStream_t stream, WsCtx& ws,
-                           StepStats* stats) {
-  const CT* Adata = (const CT*)A.data;
-  const CT* Bdata = (const CT*)B.data;
-  if (A.nd > TN_MAXR || B.nd > TN_MAXR || out_nd > TN_MAXR)
-    FAILV(TN_ERR_INVALID, "tensor rank exceeds %d", TN_MAXR);
-  auto find = [](const Meta& t, u64 lab) {
-    for (int i = 0; i < t.nd; ++i)
-      if (t.labels[i] == lab) return i;
-    return -1;
-  };
-  int apos[TN_MAXR], bpos[TN_MAXR];
-  u64 M = 1, N = 1, K = 1;
-  std::vector<int> m_out, n_out;  // positions (in out) of M legs / N legs
-  for (int i = 0; i < out_nd; ++i) {
-    apos[i] = find(A, out_labels[i]);
-    bpos[i] = find(B, out_labels[i]);
-    if (apos[i] >= 0 && bpos[i] >= 0)
-      FAILV(TN_ERR_INVALID, "out label %llu present in both inputs",
-            (unsigned long long)out_labels[i]);
-    if (apos[i] >= 0) {
-      if (A.dims[apos[i]] != out_shape[i])
-        FAILV(TN_ERR_INVALID, "dim mismatch on out label %llu",
-              (unsigned long long)out_labels[i]);
-      M *= out_shape[i];
-      m_out.push_back(i);
-    } else if (bpos[i] >= 0) {
-      if (B.dims[bpos[i]] != out_shape[i])
-        FAILV(TN_ERR_INVALID, "dim mismatch on out label %llu",
-              (unsigned long long)out_labels[i]);
-      N *= out_shape[i];
-      n_out.push_back(i);
-    } else {
-      FAILV(TN_ERR_INVALID, "out label %llu not found in inputs",
-            (unsigned long long)out_labels[i]);
-    }
-  }
-  std::vector<int> k_a, k_b;  // K legs, A order
-  for (int i = 0; i < A.nd; ++i) {
-    int j = find(B, A.labels[i]);
-    if (j >= 0) {
-      for (int o = 0; o < out_nd; ++o)
-        if (out_labels[o] == A.labels[i])
-          FAILV(TN_ERR_INVALID, "contracted label %llu appears in out",
-                (unsigned long long)A.labels[i]);
-      if (A.dims[i] != B.dims[j])
-        FAILV(TN_ERR_INVALID, "K dim mismatch on label %llu",
-              (unsigned long long)A.labels[i]);
-      K *= A.dims[i];
-      k_a.push_back(i);
-      k_b.push_back(j);
-    }
-  }
-  // every input label must be contracted (shared) or appear in out — traces
-  // and repeated labels are outside the tensor_mult boundary contract
-  // (contraction.rs:88-116 always passes the symmetric difference)
-  auto in_out = [&](u64 lab) {
-    for (int o = 0; o < out_nd; ++o)
-      if (out_labels[o] == lab) return true;
-    return false;
-  };
-  for (int i = 0; i < A.nd; ++i)
-    if (find(B, A.labels[i]) < 0 && !in_out(A.labels[i]))
-      FAILV(TN_ERR_INVALID, "label %llu of A neither contracted nor in out",
-            (unsigned long long)A.labels[i]);
-  for (int i = 0; i < B.nd; ++i)
-    if (find(A, B.labels[i]) < 0 && !in_out(B.labels[i]))
-      FAILV(TN_ERR_INVALID, "label %llu of B neither contracted nor in out",
-            (unsigned long long)B.labels[i]);
-  u64 nout = M * N;
-  if (stats) {
-    stats->m = M;
-    stats->n = N;
-    stats->k = K;
-    stats->kind = 0;
-  }
+struct Step {
+  const StepPlan& p;
+  const u64* out_shape;
+  int out_nd;
+  const Meta& A;
+  const Meta& B;
+  const CT* Adata;
+  const CT* Bdata;
+  CT* out;
+  hipStream_t stream;
+  WsCtx& ws;
+  StepStats* stats;
+};
 
-  // ---- dot: scalar output, large K ----
-  if (M == 1 && N == 1 && K > TN_SMALLK) {
-    std::vector<AxisInfo> kax;
-    for (size_t t = 0; t < k_a.size(); ++t)
-      kax.push_back({A.dims[k_a[t]], A.strides[k_a[t]], B.strides[k_b[t]]});
-    GatherMap kmap;
-    if (build_map(kax, &kmap)) FAILV(TN_ERR_INVALID, "rank too large");
-    // linear iff each axis' source stride equals its packed suffix product
-    bool linear = true;
-    {
-      i64 pstride = 1;
-      for (int i = (int)kax.size() - 1; i >= 0; --i) {
-        if (kax[i].sa != pstride || kax[i].sb != pstride) linear = false;
-        pstride *= (i64)kax[i].dim;
-      }
-    }
-    // tiled bit-permutation path: both operands are contiguous pow2 spans
-    // of the same K elements in different axis orders
-    DotPerm dp;
-    int tbits = -1;
-    if (!linear && K >= (1ull << 20)) {
-      struct BitSB {
-        u64 sa, sb;
-      };
-      std::vector<BitSB> bits;
-      bool ok = true;
-      for (auto& ax : kax) {
-        if (ax.dim == 1) continue;  // contributes no bits
-        if ((ax.dim & (ax.dim - 1)) || ax.sa <= 0 || ax.sb <= 0) {
-          ok = false;
-          break;
-        }
-        for (u64 d = 1; d < ax.dim; d <<= 1)
-          bits.push_back({(u64)ax.sa * d, (u64)ax.sb * d});
-      }
-      const int bb = TN_DOT_TILE_BBITS;
-      const int nb = (int)bits.size();
-      if (ok && nb <= TN_DOT_MAXBITS && nb > TN_DOT_TILE_ABITS + bb) {
-        std::vector<int> byA(nb), byB(nb);
-        for (int i = 0; i < nb; ++i) byA[i] = byB[i] = i;
-        std::sort(byA.begin(), byA.end(),
-                  [&](int x, int y) { return bits[x].sa < bits[y].sa; });
-        std::sort(byB.begin(), byB.end(),
-                  [&](int x, int y) { return bits[x].sb < bits[y].sb; });
-        for (int i = 0; i < nb; ++i)
-          if (bits[byA[i]].sa != (1ull << i) || bits[byB[i]].sb != (1ull << i))
-            ok = false;  // not a contiguous span on both sides
-        if (ok) {
-          std::vector<char> used(nb, 0);
-          for (int i = 0; i < TN_DOT_TILE_ABITS; ++i) {
-            used[byA[i]] = 1;
-            dp.aB[i] = bits[byA[i]].sb;
-          }
-          int nbb = 0, nr = 0;
-          for (int i = 0; i < nb && nbb < bb; ++i) {
-            const int bi = byB[i];
-            if (used[bi]) continue;
-            dp.bA[nbb] = bits[bi].sa;
-            dp.bB[nbb] = bits[bi].sb;
-            used[bi] = 1;
-            ++nbb;
-          }
-          for (int i = 0; i < nb; ++i) {
-            if (used[byA[i]]) continue;
-            dp.restA[nr] = bits[byA[i]].sa;
-            dp.restB[nr] = bits[byA[i]].sb;
-            ++nr;
-          }
-          dp.rbits = nr;
-          tbits = nr;
-        }
-      }
-    }
-    if (tbits > 0) {
-      if (stats) stats->kind = 6;  // tiled bit-permutation dot
-      const u64 nblk = 1ull << tbits;
-      double2* wsbuf;
-      {
-        int rc_ = ws_alloc(ws, (void**)&wsbuf, nblk * sizeof(double2));
-        if (rc_) return rc_;
-      }
-      k_dot_tile<CT, TN_DOT_TILE_BBITS><<<dim3((unsigned)nblk), 512, 0,
-                                           stream>>>(Adata, Bdata, wsbuf, dp);
-      k_dot_finish<<<1, 256, 0, stream>>>(wsbuf, out, (int)nblk);
-      ws_free(ws, wsbuf);
-      HIP_CHECK(hipGetLastError());
-      return TN_OK;
-    }
-    if (stats) stats->kind = linear ? 5 : 1;  // 5 = linear (streaming) dot
-    int blocks = grid_for(K);
-    if (blocks > 2048) blocks = 2048;
-    double2* wsbuf;
-    {
-      int rc_ = ws_alloc(ws, (void**)&wsbuf, blocks * sizeof(double2));
-      if (rc_) return rc_;
-    }
-    if (linear)
-      k_dot_partial_linear<<<blocks, 256, 0, stream>>>(Adata, Bdata, wsbuf, K);
-    else if (kmap.pow2)
-      k_dot_partial<true><<<blocks, 256, 0, stream>>>(Adata, Bdata, wsbuf, K,
-                                                      kmap);
-    else
-      k_dot_partial<false><<<blocks, 256, 0, stream>>>(Adata, Bdata, wsbuf, K,
-                                                       kmap);
-    k_dot_finish<<<1, 256, 0, stream>>>(wsbuf, out, blocks);
-    ws_free(ws, wsbuf);
-    HIP_CHECK(hipGetLastError());
-    return TN_OK;
+// workspace block, released on every exit from its scope
+template <typename T>
+struct WsBlock {
+  WsCtx& ws;
+  T* p = nullptr;
+  explicit WsBlock(WsCtx& w) : ws(w) {}
+  WsBlock(const WsBlock&) = delete;
+  ~WsBlock() { ws_free(ws, p); }
+  int alloc(u64 bytes) {
+    int rc = ws_alloc(ws, (void**)&p, bytes);
+    if (rc) p = nullptr;
+    return rc;
   }
+};
 
-  // ---- smallk / anyk: small K, or skinny GEMM shapes ----
-  // mid-K big shapes (e.g. M=2^20 N=2^10 K=32) run ~3x faster as a packed
-  // MFMA GEMM than as an address-gather stream
-  bool skinny = (M < 16 || N < 16);
-  bool gemm_worthy = (K >= 16 && M >= MF_T && N >= MF_TN);
-  bool gather_ok = (K <= TN_SMALLK || skinny);
-  auto run_gather = [&]() -> int {
-    if (stats) stats->kind = 0;
-    // out map: every out axis, with its source stride in A or B
-    std::vector<AxisInfo> oax;
-    for (int i = 0; i < out_nd; ++i) {
-      AxisInfo ax;
-      ax.dim = out_shape[i];
-      ax.sa = apos[i] >= 0 ? A.strides[apos[i]] : 0;
-      ax.sb = bpos[i] >= 0 ? B.strides[bpos[i]] : 0;
-      oax.push_back(ax);
-    }
-    std::vector<AxisInfo> kax;
-    for (size_t t = 0; t < k_a.size(); ++t)
-      kax.push_back({A.dims[k_a[t]], A.strides[k_a[t]], B.strides[k_b[t]]});
-    if (kax.empty()) kax.push_back({1, 0, 0});
-    bool p2 = axes_pow2(oax) && axes_pow2(kax);
-    GatherMap omap, kmap;
-    if (build_map(oax, &omap, p2) || build_map(kax, &kmap, p2))
-      FAILV(TN_ERR_INVALID, "rank too large");
-    int blocks = grid_for(nout);
-    if (K <= TN_SMALLK) {
-      // table decode pays once ~4 offsets/thread are amortized over >=8
-      // elements and the per-element decode is actually deep
-      if (p2 && nout >= (1ull << 26) && nout < (1ull << 32) && omap.n >= 8)
-        k_einsum_smallk_tbl<<<blocks > 32768 ? 32768 : blocks, 256, 0,
-                              stream>>>(Adata, Bdata, out, nout, omap, kmap,
-                                        (int)K);
-      else if (p2)
-        k_einsum_smallk<true><<<blocks, 256, 0, stream>>>(
-            Adata, Bdata, out, nout, omap, kmap, (int)K);
-      else
-        k_einsum_smallk<false><<<blocks, 256, 0, stream>>>(
-            Adata, Bdata, out, nout, omap, kmap, (int)K);
-    } else {
-      if (p2)
-        k_einsum_anyk<true><<<blocks, 256, 0, stream>>>(Adata, Bdata, out,
-                                                        nout, omap, kmap, K);
-      else
-        k_einsum_anyk<false><<<blocks, 256, 0, stream>>>(Adata, Bdata, out,
-                                                         nout, omap, kmap, K);
-    }
-    HIP_CHECK(hipGetLastError());
-    return TN_OK;
-  };
-  if (gather_ok && !gemm_worthy) return run_gather();
-
-  // ---- TTGT: pack (if needed) + GEMM + unpack (if needed) ----
-  if (stats) stats->kind = 2;
-  // GEMM operand layouts: A' = [M legs in out order][K legs in A order],
-  // B' = [K legs in A order][N legs in out order]. C = [M..][N..]; equal to
-  // `out` iff the M legs all precede the N legs there (always true for the
-  // executor's symmetric-difference order).
-  std::vector<int> a_axes;  // A axis order for A'
-  for (int p : m_out) a_axes.push_back(apos[p]);
-  for (int i : k_a) a_axes.push_back(i);
-  std::vector<int> b_axes;  // B axis order for B'
-  for (int j : k_b) b_axes.push_back(j);
-  for (int p : n_out) b_axes.push_back(bpos[p]);
-
-  auto is_ready = [](const Meta& t, const std::vector<int>& axes) {
-    if ((int)axes.size() != t.nd) return false;
-    i64 stride = 1;
-    for (int i = (int)axes.size() - 1; i >= 0; --i) {
-      if (t.strides[axes[i]] != stride) return false;
-      stride *= (i64)t.dims[axes[i]];
+// the pack pipeline's events: on every exit handed to ws.events (the walk
+// destroys them when it is over), or destroyed here when there is no list
+struct PipeEvents {
+  WsCtx& ws;
+  hipEvent_t e0 = nullptr, ep[16] = {};  // start; window w packed
+  explicit PipeEvents(WsCtx& w) : ws(w) {}
+  PipeEvents(const PipeEvents&) = delete;
+  bool create(int P) {
+    for (int w = -1; w < P; ++w) {
+      hipEvent_t& e = w < 0 ? e0 : ep[w];
+      if (hipEventCreate(&e) != hipSuccess) {
+        e = nullptr;
+        return false;
+      }
     }
     return true;
-  };
-
-  const bool needA = !is_ready(A, a_axes);
-  const bool needB = !is_ready(B, b_axes);
-  const bool mfma_shape = (M >= 32 && N >= 32);
-  // gather-staged GEMM (c128): fold the pack permutes into the GEMM's LDS
-  // staging when the shape is pure and every dim is pow2 — no pack
-  // kernels, no pack workspace, no pack HBM traffic
-  GatherGemmMap gmA{}, gmB{};
-  bool gather_gemm = false;
-  if constexpr (std::is_same_v<CT, double2>) {
-    if ((needA || needB) && mfma_shape && (M % MF_T == 0) &&
-        (N % MF_TN == 0) && (K % MF_K == 0) && !gather_gemm_disabled()) {
-      std::vector<int> a_m, b_n;
-      for (int p : m_out) a_m.push_back(apos[p]);
-      for (int p : n_out) b_n.push_back(bpos[p]);
-      gather_gemm = build_ggmap(A, a_m, k_a, &gmA) &&
-                    build_ggmap(B, b_n, k_b, &gmB);
-    }
   }
-
-  // does C == out directly? (decided before packing so the pack-pipeline
-  // below can target the right C buffer)
-  bool direct = true;
-  if (!m_out.empty() && !n_out.empty() && m_out.back() > n_out.front())
-    direct = false;
-  CT* Cg = out;
-  CT* tmpC = nullptr;
-  if (!direct) {
-    if (stats) stats->kind = 3;
-    {
-      int rc_ = ws_alloc(ws, (void**)&tmpC, nout * sizeof(CT));
-      if (rc_ == TN_ERR_OOM && gather_ok) return run_gather();
-      if (rc_) return rc_;
-    }
-    Cg = tmpC;
+  void drop(hipEvent_t e) {
+    if (e && ws.events)
+      ws.events->push_back(e);
+    else if (e)
+      (void)hipEventDestroy(e);
   }
-
-  // ---- pack-pipeline: chunk the pack over K windows and overlap each
-  // window's permute (stream2) with the previous window's GEMM (stream).
-  // The window GEMMs write split-K-style slices reduced at the end, so no
-  // kernel changes are needed; the pack permutes (HBM-bound, ~4 TB/s)
-  // ride in the MFMA-bound GEMM's spare bandwidth. Applied when the model
-  // predicts a net win over the serial pack (the slice buffers cost
-  // (2p)·M·N extra traffic). Requires a packed A (a ready A's K-windows
-  // are strided); B may be packed or ready (row windows are contiguous).
-  bool pipelined = false;
-  if (ws.stream2 && needA && mfma_shape && (M % MF_T == 0) &&
-      (N % MF_TN == 0) && (K % MF_K == 0) && !pipeline_disabled()) {
-    u64 packbytes =
-        ((needA ? M * K : 0) + (needB ? K * N : 0)) * sizeof(CT);
-    double best_save = 0.0;
-    int best_p = 0, best_npre = 0, feas_p = 0, feas_npre = 0;
-    u64 best_kc = 0, feas_kc = 0;
-    {
-      u64 p = 1;
-      u64 tiles_w = (M / MF_T) * ((N + MF_TN - 1) / MF_TN);
-      for (size_t x = 0; x < k_a.size() && p < 16; ++x) {
-        p *= A.dims[k_a[x]];
-        if (p < 2 || p > 16) continue;
-        u64 kc = K / p;
-        if (kc % MF_K || tiles_w < 256) continue;
-        double save = 2.0 * (double)packbytes / 4e12 * (1.0 - 1.0 / p) -
-                      2.0 * p * (double)(M * N * sizeof(CT)) / 6e12;
-        feas_p = (int)p;
-        feas_kc = kc;
-        feas_npre = (int)(x + 1);
-        if (save > best_save) {
-          best_save = save;
-          best_p = (int)p;
-          best_kc = kc;
-          best_npre = (int)(x + 1);
-        }
-      }
-    }
-    // measured gate (r02 A/B on hardware): marginal steps LOSE to the
-    // serial pack (window-launch overhead + slice-reduce traffic), so
-    // pipeline only when the predicted win is substantial and the pack
-    // dwarfs the output (rqc36's 4-10x-ratio steps regressed ~12 ms;
-    // syc49's 64x step gains ~12 ms)
-    if (pipeline_forced() && feas_p) {
-      best_p = feas_p;
-      best_kc = feas_kc;
-      best_npre = feas_npre;
-    } else if (best_p &&
-               (best_save <= 5e-3 ||
-                (double)packbytes < 8.0 * (double)(M * N * sizeof(CT))))
-      best_p = 0;
-    if (best_p) {
-      const int P = best_p;
-      const u64 kc = best_kc;
-      CT* Awin = nullptr;
-      CT* Bwin = nullptr;
-      CT* slices = nullptr;
-      int rc_ = ws_alloc(ws, (void**)&Awin, M * K * sizeof(CT));
-      if (rc_ == TN_OK && needB)
-        rc_ = ws_alloc(ws, (void**)&Bwin, K * N * sizeof(CT));
-      if (rc_ == TN_OK)
-        rc_ = ws_alloc(ws, (void**)&slices, (u64)P * nout * sizeof(CT));
-      hipEvent_t e0 = nullptr, ep[16] = {};
-      bool ev_ok = (rc_ == TN_OK);
-      if (ev_ok && hipEventCreate(&e0) != hipSuccess) {
-        e0 = nullptr;
-        ev_ok = false;
-      }
-      for (int w = 0; ev_ok && w < P; ++w)
-        if (hipEventCreate(&ep[w]) != hipSuccess) {
-          ep[w] = nullptr;
-          ev_ok = false;
-        }
-      if (!ev_ok) {
-        // shortage: fall through to the serial pack path
-        ws_free(ws, Awin);
-        ws_free(ws, Bwin);
-        ws_free(ws, slices);
-        if (ws.events) {
-          if (e0) ws.events->push_back(e0);
-          for (int w = 0; w < P; ++w)
-            if (ep[w]) ws.events->push_back(ep[w]);
-        } else {
-          if (e0) (void)hipEventDestroy(e0);
-          for (int w = 0; w < P; ++w)
-            if (ep[w]) (void)hipEventDestroy(ep[w]);
-        }
-      } else {
-        // mixed-radix suffix products of the leading K legs (window digit
-        // x has radix A.dims[k_a[x]])
-        u64 sufA[16] = {};
-        {
-          u64 s = 1;
-          for (int x = best_npre - 1; x >= 0; --x) {
-            sufA[x] = s;
-            s *= A.dims[k_a[x]];
-          }
-        }
-        HIP_CHECK(hipEventRecord(e0, stream));
-        HIP_CHECK(hipStreamWaitEvent(ws.stream2, e0, 0));
-        for (int w = 0; w < P; ++w) {
-          // source offsets of window w
-          u64 offA = 0, offB = 0;
-          for (int x = 0; x < best_npre; ++x) {
-            u64 digit = ((u64)w / sufA[x]) % A.dims[k_a[x]];
-            offA += digit * (u64)A.strides[k_a[x]];
-            offB += digit * (u64)B.strides[k_b[x]];
-          }
-          {
-            std::vector<AxisInfo> ax;
-            for (int p2 : m_out)
-              ax.push_back({A.dims[apos[p2]], A.strides[apos[p2]], 0});
-            for (size_t x = best_npre; x < k_a.size(); ++x)
-              ax.push_back({A.dims[k_a[x]], A.strides[k_a[x]], 0});
-            int prc = launch_permute(Adata + offA, Awin + (u64)w * M * kc,
-                                     M * kc, ax, ws.stream2);
-            if (prc) return prc;
-          }
-          if (needB) {
-            std::vector<AxisInfo> ax;
-            for (size_t x = best_npre; x < k_b.size(); ++x)
-              ax.push_back({B.dims[k_b[x]], B.strides[k_b[x]], 0});
-            for (int p2 : n_out)
-              ax.push_back({B.dims[bpos[p2]], B.strides[bpos[p2]], 0});
-            int prc = launch_permute(Bdata + offB, Bwin + (u64)w * kc * N,
-                                     kc * N, ax, ws.stream2);
-            if (prc) return prc;
-          }
-          HIP_CHECK(hipEventRecord(ep[w], ws.stream2));
-        }
-        u64 tiles_w = (M / MF_T) * (N / MF_TN);
-        if (stats && stats->gemm_ev0)
-          HIP_CHECK(hipEventRecord(stats->gemm_ev0, stream));
-        for (int w = 0; w < P; ++w) {
-          HIP_CHECK(hipStreamWaitEvent(stream, ep[w], 0));
-          const CT* Aw = Awin + (u64)w * M * kc;
-          const CT* Bw = needB ? Bwin + (u64)w * kc * N
-                               : Bdata + (u64)w * kc * N;
-          CT* Cw = slices + (u64)w * nout;
-          if constexpr (std::is_same_v<CT, double2>) {
-            k_zgemm_c128_glds_pure<<<dim3((unsigned)tiles_w), MF_THREADS, 0,
-                                     stream>>>(
-                Aw, Bw, Cw, M, N, kc, (unsigned)(N / MF_TN),
-                (unsigned)tiles_w, kc);
-          } else {
-            k_zgemm_c64_glds_pure<<<dim3((unsigned)tiles_w), MF_THREADS, 0,
-                                    stream>>>(
-                (const float2*)Aw, (const float2*)Bw, (float2*)Cw, M, N, kc,
-                (unsigned)(N / MF_TN), (unsigned)tiles_w, kc);
-          }
-        }
-        k_splitk_reduce<<<grid_for(nout), 256, 0, stream>>>(slices, Cg,
-                                                            nout, P);
-        if (stats && stats->gemm_ev1)
-          HIP_CHECK(hipEventRecord(stats->gemm_ev1, stream));
-        HIP_CHECK(hipGetLastError());
-        ws_free(ws, Awin);
-        ws_free(ws, Bwin);
-        ws_free(ws, slices);
-        if (ws.events) {
-          ws.events->push_back(e0);
-          for (int w = 0; w < P; ++w) ws.events->push_back(ep[w]);
-        } else {
-          (void)hipEventDestroy(e0);
-          for (int w = 0; w < P; ++w) (void)hipEventDestroy(ep[w]);
-        }
-        pipelined = true;
-      }
-    }
+  ~PipeEvents() {
+    drop(e0);
+    for (hipEvent_t e : ep) drop(e);
   }
-  if (pipelined) {
-    if (!direct) {
-      std::vector<i64> tmp_stride(out_nd, 0);
-      i64 stride = 1;
-      for (int t = (int)n_out.size() - 1; t >= 0; --t) {
-        tmp_stride[n_out[t]] = stride;
-        stride *= (i64)out_shape[n_out[t]];
-      }
-      for (int t = (int)m_out.size() - 1; t >= 0; --t) {
-        tmp_stride[m_out[t]] = stride;
-        stride *= (i64)out_shape[m_out[t]];
-      }
-      std::vector<AxisInfo> ax;
-      for (int i = 0; i < out_nd; ++i)
-        ax.push_back({out_shape[i], tmp_stride[i], 0});
-      int rc_ = launch_permute((const CT*)tmpC, out, nout, ax, stream);
-      if (rc_) return rc_;
-    }
-    ws_free(ws, tmpC);
+};
+
+// K axes with their strides in A and B
+static std::vector<AxisInfo> k_axis_info(const StepPlan& p, const Meta& A,
+                                         const Meta& B) {
+  std::vector<AxisInfo> kax;
+  for (int t = 0; t < p.k_a.n; ++t)
+    kax.push_back(
+        {A.dims[p.k_a[t]], A.strides[p.k_a[t]], B.strides[p.k_b[t]]});
+  return kax;
+}
+
+// ---- dot: scalar output, large K ----
+template <typename CT>
+static int run_dot(const Step<CT>& s) {
+  const StepPlan& p = s.p;
+  const int blocks = (int)p.dot_blocks;
+  GatherMap kmap;
+  if (p.dot_form == TN_DOT_GATHER &&
+      build_map(k_axis_info(p, s.A, s.B), &kmap))
+    FAILV(TN_ERR_INVALID, "rank too large");
+  WsBlock<double2> wsbuf(s.ws);
+  if (int rc = wsbuf.alloc(p.dot_blocks * sizeof(double2))) return rc;
+  if (p.dot_form == TN_DOT_TILED) {
+    // (finishes here, not below: the order in which the kernel templates
+    // are first used fixes their order in the code object)
+    k_dot_tile<CT, TN_DOT_TILE_BBITS><<<dim3((unsigned)p.dot_blocks), 512, 0,
+                                         s.stream>>>(s.Adata, s.Bdata,
+                                                     wsbuf.p, p.dp);
+    k_dot_finish<<<1, 256, 0, s.stream>>>(wsbuf.p, s.out, blocks);
+    HIP_CHECK(hipGetLastError());
     return TN_OK;
   }
+  if (p.dot_form == TN_DOT_LINEAR)
+    k_dot_partial_linear<<<blocks, 256, 0, s.stream>>>(s.Adata, s.Bdata,
+                                                       wsbuf.p, p.k);
+  else if (kmap.pow2)
+    k_dot_partial<true><<<blocks, 256, 0, s.stream>>>(s.Adata, s.Bdata,
+                                                      wsbuf.p, p.k, kmap);
+  else
+    k_dot_partial<false><<<blocks, 256, 0, s.stream>>>(s.Adata, s.Bdata,
+                                                       wsbuf.p, p.k, kmap);
+  k_dot_finish<<<1, 256, 0, s.stream>>>(wsbuf.p, s.out, blocks);
+  HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
 
-  const CT* Ag = Adata;
-  const CT* Bg = Bdata;
-  CT* packA = nullptr;
-  CT* packB = nullptr;
-  if (!gather_gemm && needA) {
-    std::vector<AxisInfo> ax;
-    for (int axis : a_axes) ax.push_back({A.dims[axis], A.strides[axis], 0});
-    u64 elems = M * K;
-    {
-      int rc_ = ws_alloc(ws, (void**)&packA, elems * sizeof(CT));
-      // pack workspace doesn't fit -> run the shape through the (slower)
-      // gather kernels instead of failing the whole contraction
-      if (rc_ == TN_ERR_OOM && gather_ok) {
-        ws_free(ws, tmpC);
-        return run_gather();
-      }
-      if (rc_) return rc_;
-    }
-    {
-      int rc_ = launch_permute(Adata, packA, elems, ax, stream);
-      if (rc_) return rc_;
-    }
-    Ag = packA;
+// ---- smallk / anyk: small K, or skinny GEMM shapes; also where a TTGT step
+// goes when its workspace does not fit and the plan says gather_ok ----
+template <typename CT>
+static int run_gather(const Step<CT>& s) {
+  const StepPlan& p = s.p;
+  const u64 nout = p.nout(), K = p.k;
+  if (s.stats) s.stats->kind = 0;
+  // out map: every out axis, with its source stride in A or B
+  std::vector<AxisInfo> oax;
+  for (int i = 0; i < s.out_nd; ++i) {
+    AxisInfo ax;
+    ax.dim = s.out_shape[i];
+    ax.sa = p.apos[i] >= 0 ? s.A.strides[p.apos[i]] : 0;
+    ax.sb = p.bpos[i] >= 0 ? s.B.strides[p.bpos[i]] : 0;
+    oax.push_back(ax);
   }
-  if (!gather_gemm && needB) {
-    std::vector<AxisInfo> ax;
-    for (int axis : b_axes) ax.push_back({B.dims[axis], B.strides[axis], 0});
-    u64 elems = K * N;
-    {
-      int rc_ = ws_alloc(ws, (void**)&packB, elems * sizeof(CT));
-      if (rc_ == TN_ERR_OOM && gather_ok) {
-        ws_free(ws, packA);
-        ws_free(ws, tmpC);
-        return run_gather();
-      }
-      if (rc_) return rc_;
-    }
-    {
-      int rc_ = launch_permute(Bdata, packB, elems, ax, stream);
-      if (rc_) return rc_;
-    }
-    Bg = packB;
+  std::vector<AxisInfo> kax = k_axis_info(p, s.A, s.B);
+  if (kax.empty()) kax.push_back({1, 0, 0});
+  bool p2 = axes_pow2(oax) && axes_pow2(kax);
+  GatherMap omap, kmap;
+  if (build_map(oax, &omap, p2) || build_map(kax, &kmap, p2))
+    FAILV(TN_ERR_INVALID, "rank too large");
+  int blocks = grid_for(nout);
+  if (K <= TN_SMALLK) {
+    // table decode pays once ~4 offsets/thread are amortized over >=8
+    // elements and the per-element decode is actually deep
+    if (p2 && nout >= (1ull << 26) && nout < (1ull << 32) && omap.n >= 8)
+      k_einsum_smallk_tbl<<<blocks > 32768 ? 32768 : blocks, 256, 0,
+                            s.stream>>>(s.Adata, s.Bdata, s.out, nout, omap,
+                                        kmap, (int)K);
+    else if (p2)
+      k_einsum_smallk<true><<<blocks, 256, 0, s.stream>>>(
+          s.Adata, s.Bdata, s.out, nout, omap, kmap, (int)K);
+    else
+      k_einsum_smallk<false><<<blocks, 256, 0, s.stream>>>(
+          s.Adata, s.Bdata, s.out, nout, omap, kmap, (int)K);
+  } else {
+    if (p2)
+      k_einsum_anyk<true><<<blocks, 256, 0, s.stream>>>(
+          s.Adata, s.Bdata, s.out, nout, omap, kmap, K);
+    else
+      k_einsum_anyk<false><<<blocks, 256, 0, s.stream>>>(
+          s.Adata, s.Bdata, s.out, nout, omap, kmap, K);
   }
+  HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
 
-  bool mfma = mfma_shape;
-  u64 row_tile_h = mfma ? MF_T : GT;
-  u64 row_tiles = (M + row_tile_h - 1) / row_tile_h;
-  u64 col_tiles = (N + GT - 1) / GT;
-  u64 tiles = row_tiles * col_tiles;
-  // split-K: with few tiles and deep K, slice K across extra blocks into
-  // partial buffers + a reduce pass (fills the 256 CUs; a 64-tile K=2^20
-  // GEMM goes from ~6 to ~50 TFLOP/s)
-  u64 splitk = 1;
-  if (tiles < 192 && K >= 256) {
-    while (tiles * splitk < 256 && K / (splitk * 2) >= 64) splitk *= 2;
-    if (splitk > 64) splitk = 64;
+// ---- pipelined TTGT: window w's pack permutes run on stream2 while window
+// w-1's GEMM runs on stream; the window GEMMs write split-K-style slices,
+// reduced into Cg at the end. *done stays false when the window buffers or
+// the events cannot be had: the caller then packs serially.
+template <typename CT>
+static int ttgt_pipelined(const Step<CT>& s, CT* Cg, bool* done) {
+  const StepPlan& p = s.p;
+  const Meta& A = s.A;
+  const Meta& B = s.B;
+  const u64 M = p.m, N = p.n, K = p.k, nout = p.nout();
+  const int P = p.pipe_p, npre = p.pipe_npre;
+  const u64 kc = p.pipe_kc;
+  PipeEvents ev(s.ws);
+  WsBlock<CT> slices(s.ws), Bwin(s.ws), Awin(s.ws);
+  int rc_ = Awin.alloc(M * K * sizeof(CT));
+  if (rc_ == TN_OK && p.pack_b) rc_ = Bwin.alloc(K * N * sizeof(CT));
+  if (rc_ == TN_OK) rc_ = slices.alloc((u64)P * nout * sizeof(CT));
+  if (rc_ != TN_OK || !ev.create(P)) return TN_OK;  // shortage
+  // mixed-radix suffix products of the leading K legs (window digit x has
+  // radix A.dims[k_a[x]])
+  u64 sufA[16] = {};
+  {
+    u64 suf = 1;
+    for (int x = npre - 1; x >= 0; --x) {
+      sufA[x] = suf;
+      suf *= A.dims[p.k_a[x]];
+    }
   }
-  u64 kchunk = (K + splitk - 1) / splitk;
-  kchunk = ((kchunk + MF_K - 1) / MF_K) * MF_K;  // tile-aligned
-  splitk = (K + kchunk - 1) / kchunk;
+  HIP_CHECK(hipEventRecord(ev.e0, s.stream));
+  HIP_CHECK(hipStreamWaitEvent(s.ws.stream2, ev.e0, 0));
+  for (int w = 0; w < P; ++w) {
+    // source offsets of window w
+    u64 offA = 0, offB = 0;
+    for (int x = 0; x < npre; ++x) {
+      u64 digit = ((u64)w / sufA[x]) % A.dims[p.k_a[x]];
+      offA += digit * (u64)A.strides[p.k_a[x]];
+      offB += digit * (u64)B.strides[p.k_b[x]];
+    }
+    {
+      std::vector<AxisInfo> ax;
+      for (int o : p.m_out)
+        ax.push_back({A.dims[p.apos[o]], A.strides[p.apos[o]], 0});
+      for (int x = npre; x < p.k_a.n; ++x)
+        ax.push_back({A.dims[p.k_a[x]], A.strides[p.k_a[x]], 0});
+      int prc = launch_permute(s.Adata + offA, Awin.p + (u64)w * M * kc,
+                               M * kc, ax, s.ws.stream2);
+      if (prc) return prc;
+    }
+    if (p.pack_b) {
+      std::vector<AxisInfo> ax;
+      for (int x = npre; x < p.k_b.n; ++x)
+        ax.push_back({B.dims[p.k_b[x]], B.strides[p.k_b[x]], 0});
+      for (int o : p.n_out)
+        ax.push_back({B.dims[p.bpos[o]], B.strides[p.bpos[o]], 0});
+      int prc = launch_permute(s.Bdata + offB, Bwin.p + (u64)w * kc * N,
+                               kc * N, ax, s.ws.stream2);
+      if (prc) return prc;
+    }
+    HIP_CHECK(hipEventRecord(ev.ep[w], s.ws.stream2));
+  }
+  u64 tiles_w = (M / MF_T) * (N / MF_TN);
+  if (s.stats && s.stats->gemm_ev0)
+    HIP_CHECK(hipEventRecord(s.stats->gemm_ev0, s.stream));
+  for (int w = 0; w < P; ++w) {
+    HIP_CHECK(hipStreamWaitEvent(s.stream, ev.ep[w], 0));
+    const CT* Aw = Awin.p + (u64)w * M * kc;
+    const CT* Bw =
+        p.pack_b ? Bwin.p + (u64)w * kc * N : s.Bdata + (u64)w * kc * N;
+    CT* Cw = slices.p + (u64)w * nout;
+    if constexpr (std::is_same_v<CT, double2>) {
+      k_zgemm_c128_glds_pure<<<dim3((unsigned)tiles_w), MF_THREADS, 0,
+                               s.stream>>>(Aw, Bw, Cw, M, N, kc,
+                                           (unsigned)(N / MF_TN),
+                                           (unsigned)tiles_w, kc);
+    } else {
+      k_zgemm_c64_glds_pure<<<dim3((unsigned)tiles_w), MF_THREADS, 0,
+                              s.stream>>>(
+          (const float2*)Aw, (const float2*)Bw, (float2*)Cw, M, N, kc,
+          (unsigned)(N / MF_TN), (unsigned)tiles_w, kc);
+    }
+  }
+  k_splitk_reduce<<<grid_for(nout), 256, 0, s.stream>>>(slices.p, Cg, nout,
+                                                        P);
+  if (s.stats && s.stats->gemm_ev1)
+    HIP_CHECK(hipEventRecord(s.stats->gemm_ev1, s.stream));
+  HIP_CHECK(hipGetLastError());
+  *done = true;
+  return TN_OK;
+}
+
+// ---- serial TTGT: pack (if needed) + GEMM into Cg. The pack blocks belong
+// to the caller, which keeps them until the out permute is launched. Returns
+// TN_ERR_OOM only when a pack buffer could not be had.
+template <typename CT>
+static int ttgt_serial(const Step<CT>& s, CT* Cg, WsBlock<CT>& packA,
+                       WsBlock<CT>& packB) {
+  const StepPlan& p = s.p;
+  const u64 M = p.m, N = p.n, K = p.k, nout = p.nout();
+  const CT* Ag = s.Adata;
+  const CT* Bg = s.Bdata;
+  auto pack = [&](const Meta& t, const AxisList& axes, u64 elems,
+                  WsBlock<CT>& blk, const CT** src) -> int {
+    std::vector<AxisInfo> ax;
+    for (int axis : axes) ax.push_back({t.dims[axis], t.strides[axis], 0});
+    if (int rc_ = blk.alloc(elems * sizeof(CT))) return rc_;
+    if (int rc_ = launch_permute(*src, blk.p, elems, ax, s.stream)) return rc_;
+    *src = blk.p;
+    return TN_OK;
+  };
+  if (!p.gather_gemm && p.pack_a)
+    if (int rc_ = pack(s.A, p.a_axes, M * K, packA, &Ag)) return rc_;
+  if (!p.gather_gemm && p.pack_b)
+    if (int rc_ = pack(s.B, p.b_axes, K * N, packB, &Bg)) return rc_;
+
+  const u64 tiles = p.row_tiles * p.col_tiles;
+  u64 splitk = p.splitk, kchunk = p.kchunk;
   CT* gemm_out = Cg;
-  CT* splitbuf = nullptr;
+  WsBlock<CT> splitbuf(s.ws);
   if (splitk > 1) {
-    int rc_ = ws_alloc(ws, (void**)&splitbuf, splitk * nout * sizeof(CT));
+    int rc_ = splitbuf.alloc(splitk * nout * sizeof(CT));
     if (rc_ == TN_ERR_OOM) {
       splitk = 1;  // split-K is an optimization; run unsplit when tight
       kchunk = ((K + MF_K - 1) / MF_K) * MF_K;
     } else if (rc_) {
       return rc_;
     } else {
-      gemm_out = splitbuf;
+      gemm_out = splitbuf.p;
     }
   }
-  dim3 grid((unsigned)(tiles * splitk));
-  if (stats && stats->gemm_ev0)
-    HIP_CHECK(hipEventRecord(stats->gemm_ev0, stream));
-  if (mfma) {
-    if constexpr (std::is_same_v<CT, double2>) {
-      bool pure = (M % MF_T == 0) && (N % MF_TN == 0) && (K % MF_K == 0) &&
-                  (kchunk % MF_K == 0);
-      // 3M routing: pure, unsplit, not a gather-GEMM step (pipeline windows
-      // returned above) and past the profitability gate; "force" drops the
-      // gate and the unsplit condition
-      const int m3 = gemm3m_mode();
-      const bool use_3m =
-          pure && !gather_gemm && m3 != GEMM3M_OFF && gemm3m_fits(N, K) &&
-          (m3 == GEMM3M_FORCE ||
-           (splitk == 1 && gemm3m_profitable(K, tiles)));
-      // gather_gemm implies pure: its precondition covers M/N/K tiling and
-      // kchunk is MF_K-rounded above
-      if (gather_gemm)
-        k_zgemm_c128_glds_gather<<<grid, MF_THREADS, 0, stream>>>(
-            Adata, Bdata, gemm_out, M, N, K, (unsigned)col_tiles,
-            (unsigned)tiles, kchunk, gmA, gmB);
-      else if (pure && use_3m)
-        k_zgemm_c128_glds_3m<<<grid, MF3_THREADS, 0, stream>>>(
-            Ag, Bg, gemm_out, M, N, K, (unsigned)col_tiles, (unsigned)tiles,
-            kchunk);
-      else if (pure)
-        k_zgemm_c128_glds_pure<<<grid, MF_THREADS, 0, stream>>>(
-            Ag, Bg, gemm_out, M, N, K, (unsigned)col_tiles, (unsigned)tiles,
-            kchunk);
-      else
-        k_zgemm_c128_glds<<<grid, MF_THREADS, 0, stream>>>(
-            Ag, Bg, gemm_out, M, N, K, (unsigned)col_tiles, (unsigned)tiles,
-            kchunk);
-    } else {
-      bool pure = (M % MF_T == 0) && (N % MF_TN == 0) && (K % MF_K == 0) &&
-                  (kchunk % MF_K == 0);
-      if (pure)
-        k_zgemm_c64_glds_pure<<<grid, MF_THREADS, 0, stream>>>(
-            (const float2*)Ag, (const float2*)Bg, (float2*)gemm_out, M, N, K,
-            (unsigned)col_tiles, (unsigned)tiles, kchunk);
-      else
-        k_zgemm_mfma<<<grid, MF_THREADS, 0, stream>>>(
-            Ag, Bg, gemm_out, M, N, K, (unsigned)col_tiles, (unsigned)tiles,
-            kchunk);
-    }
+  const dim3 grid((unsigned)(tiles * splitk));
+  const unsigned ct = (unsigned)p.col_tiles, nt = (unsigned)tiles;
+  if (s.stats && s.stats->gemm_ev0)
+    HIP_CHECK(hipEventRecord(s.stats->gemm_ev0, s.stream));
+  // the c128 kernels exist for double2 only, the c64 ones for float2
+  if constexpr (std::is_same_v<CT, double2>) {
+    if (p.kernel == TN_GEMM_C128_GATHER)
+      k_zgemm_c128_glds_gather<<<grid, MF_THREADS, 0, s.stream>>>(
+          s.Adata, s.Bdata, gemm_out, M, N, K, ct, nt, kchunk, p.gmA, p.gmB);
+    else if (p.kernel == TN_GEMM_C128_3M)
+      k_zgemm_c128_glds_3m<<<grid, MF3_THREADS, 0, s.stream>>>(
+          Ag, Bg, gemm_out, M, N, K, ct, nt, kchunk);
+    else if (p.kernel == TN_GEMM_C128_PURE)
+      k_zgemm_c128_glds_pure<<<grid, MF_THREADS, 0, s.stream>>>(
+          Ag, Bg, gemm_out, M, N, K, ct, nt, kchunk);
+    else if (p.kernel == TN_GEMM_C128_GLDS)
+      k_zgemm_c128_glds<<<grid, MF_THREADS, 0, s.stream>>>(
+          Ag, Bg, gemm_out, M, N, K, ct, nt, kchunk);
   } else {
-    k_zgemm_v1<<<grid, 256, 0, stream>>>(Ag, Bg, gemm_out, M, N, K,
-                                         (unsigned)col_tiles, (unsigned)tiles,
-                                         kchunk);
+    if (p.kernel == TN_GEMM_C64_PURE)
+      k_zgemm_c64_glds_pure<<<grid, MF_THREADS, 0, s.stream>>>(
+          (const float2*)Ag, (const float2*)Bg, (float2*)gemm_out, M, N, K,
+          ct, nt, kchunk);
+    else if (p.kernel == TN_GEMM_MFMA)
+      k_zgemm_mfma<<<grid, MF_THREADS, 0, s.stream>>>(Ag, Bg, gemm_out, M, N,
+                                                      K, ct, nt, kchunk);
   }
+  if (p.kernel == TN_GEMM_V1)
+    k_zgemm_v1<<<grid, 256, 0, s.stream>>>(Ag, Bg, gemm_out, M, N, K, ct, nt,
+                                           kchunk);
   if (splitk > 1)
-    k_splitk_reduce<<<grid_for(nout), 256, 0, stream>>>(splitbuf, Cg, nout,
-                                                        (int)splitk);
-  if (stats && stats->gemm_ev1)
-    HIP_CHECK(hipEventRecord(stats->gemm_ev1, stream));
+    k_splitk_reduce<<<grid_for(nout), 256, 0, s.stream>>>(splitbuf.p, Cg,
+                                                          nout, (int)splitk);
+  if (s.stats && s.stats->gemm_ev1)
+    HIP_CHECK(hipEventRecord(s.stats->gemm_ev1, s.stream));
   HIP_CHECK(hipGetLastError());
-  if (splitbuf) ws_free(ws, splitbuf);
-
-  if (!direct) {
-    // permute tmp [M legs (out order)][N legs (out order)] -> out order
-    // source strides of each out axis inside tmp:
-    std::vector<i64> tmp_stride(out_nd, 0);
-    i64 stride = 1;
-    for (int t = (int)n_out.size() - 1; t >= 0; --t) {
-      tmp_stride[n_out[t]] = stride;
-      stride *= (i64)out_shape[n_out[t]];
-    }
-    for (int t = (int)m_out.size() - 1; t >= 0; --t) {
-      tmp_stride[m_out[t]] = stride;
-      stride *= (i64)out_shape[m_out[t]];
-    }
-    std::vector<AxisInfo> ax;
-    for (int i = 0; i < out_nd; ++i)
-      ax.push_back({out_shape[i], tmp_stride[i], 0});
-    {
-      int rc_ = launch_permute((const CT*)tmpC, out, nout, ax, stream);
-      if (rc_) return rc_;
-    }
-  }
-  ws_free(ws, packA);
-  ws_free(ws, packB);
-  ws_free(ws, tmpC);
   return TN_OK;
+}
+
+// ---- TTGT: GEMM into `out`, or into a temporary C that is then permuted
+// into out order ----
+template <typename CT>
+static int run_ttgt(const Step<CT>& s) {
+  const StepPlan& p = s.p;
+  // released in the order packA, packB, tmpC
+  WsBlock<CT> tmpC(s.ws), packB(s.ws), packA(s.ws);
+  CT* Cg = s.out;
+  int rc_ = TN_OK;
+  if (!p.direct) {
+    rc_ = tmpC.alloc(p.nout() * sizeof(CT));
+    Cg = tmpC.p;
+  }
+  bool pipelined = false;
+  if (rc_ == TN_OK && p.pipe_p) rc_ = ttgt_pipelined(s, Cg, &pipelined);
+  if (rc_ == TN_OK && !pipelined) rc_ = ttgt_serial(s, Cg, packA, packB);
+  // the temporary C or a pack buffer doesn't fit -> run the shape through
+  // the (slower) gather kernels instead of failing the whole contraction
+  if (rc_ == TN_ERR_OOM && p.gather_ok) return run_gather(s);
+  if (rc_ || p.direct) return rc_;
+  // permute tmp [M legs (out order)][N legs (out order)] -> out order;
+  // source strides of each out axis inside tmp:
+  std::vector<i64> tmp_stride(s.out_nd, 0);
+  i64 stride = 1;
+  for (int t = p.n_out.n - 1; t >= 0; --t) {
+    tmp_stride[p.n_out[t]] = stride;
+    stride *= (i64)s.out_shape[p.n_out[t]];
+  }
+  for (int t = p.m_out.n - 1; t >= 0; --t) {
+    tmp_stride[p.m_out[t]] = stride;
+    stride *= (i64)s.out_shape[p.m_out[t]];
+  }
+  std::vector<AxisInfo> ax;
+  for (int i = 0; i < s.out_nd; ++i)
+    ax.push_back({s.out_shape[i], tmp_stride[i], 0});
+  return launch_permute((const CT*)tmpC.p, s.out, p.nout(), ax, s.stream);
+}
+
+template <typename CT>
+static int einsum_dev_impl(const u64* out_labels, const u64* out_shape,
+                           int out_nd, const Meta& A, const Meta& B,
+                           CT* out, hipStream_t stream, WsCtx& ws,
+                           StepStats* stats) {
+  StepPlan plan;
+  std::string err;
+  if (int rc = plan_step(std::is_same_v<CT, double2>, out_labels, out_shape,
+                         out_nd, A, B, ws.stream2 != nullptr, &plan, &err)) {
+    g_last_error = err;
+    return rc;
+  }
+  if (stats) {
+    stats->m = plan.m;
+    stats->n = plan.n;
+    stats->k = plan.k;
+    stats->kind = plan.kind;
+  }
+  const Step<CT> s{plan, out_shape, out_nd, A, B, (const CT*)A.data,
+                   (const CT*)B.data, out, stream, ws, stats};
+  if (plan.route == TN_ROUTE_DOT) return run_dot(s);
+  if (plan.route == TN_ROUTE_GATHER) return run_gather(s);
+  return run_ttgt(s);
 }
 
 // ---------------------------------------------------------------------------
@@ -2288,6 +1884,33 @@ extern "C" int tn_einsum_c64_dev(const u64* out_labels, const u64* out_shape,
                                   a_shape, a_strides, a_dev, a_ndim, b_labels,
                                   b_shape, b_strides, b_dev, b_ndim, out_dev,
                                   stream);
+}
+
+// the plan einsum_dev_impl would act on; no GPU needed, none touched
+extern "C" int tn_plan_step(int dtype, const u64* out_labels,
+                            const u64* out_shape, size_t out_ndim,
+                            const u64* a_labels, const u64* a_shape,
+                            const i64* a_strides, size_t a_ndim,
+                            const u64* b_labels, const u64* b_shape,
+                            const i64* b_strides, size_t b_ndim,
+                            int has_stream2, tn_step_plan* plan) {
+  if (!plan || (dtype != 0 && dtype != 1) || out_ndim > TN_MAXR)
+    FAILV(TN_ERR_INVALID, "null plan, unknown dtype or rank over %d", TN_MAXR);
+  Meta A, B;
+  int rc = fill_meta(&A, a_labels, a_shape, a_strides, nullptr, a_ndim);
+  if (rc) return rc;
+  rc = fill_meta(&B, b_labels, b_shape, b_strides, nullptr, b_ndim);
+  if (rc) return rc;
+  StepPlan p;
+  std::string err;
+  rc = plan_step(dtype == 0, out_labels, out_shape, (int)out_ndim, A, B,
+                 has_stream2 != 0, &p, &err);
+  if (rc) {
+    g_last_error = err;
+    return rc;
+  }
+  *plan = p;
+  return TN_OK;
 }
 
 static u64 span_elems(const u64* shape, const i64* strides, size_t nd) {
@@ -2533,14 +2156,13 @@ static void symdiff(const DevTensor& a, const DevTensor& b,
 }
 
 // ---- pack-overlap planning ------------------------------------------------
-// Mirror of einsum_dev_impl's dispatch, host-side and launch-free: would the
-// step take the TTGT route, and which operands would it pack? Used by the
-// walk to pre-permute the NEXT step's GEMM operands on a second stream while
-// the current step's GEMM runs (the GEMMs are MFMA-bound and use <10% of the
-// HBM bandwidth the permutes need, so the packs ride along ~free). Any
-// divergence from the real dispatch is performance-only: a prepacked operand
-// is a valid contiguous tensor in pack order, every kernel class consumes it
-// correctly, and an operand NOT prepacked is packed inline as before.
+// Would the step take the TTGT route, and which operands would it pack? Asked
+// of the same planner the dispatch uses. The walk pre-permutes the NEXT
+// step's GEMM operands on a second stream while the current step's GEMM runs
+// (the GEMMs are MFMA-bound and use <10% of the HBM bandwidth the permutes
+// need, so the packs ride along ~free). A prepacked operand is a valid
+// contiguous tensor in pack order, which the step then finds ready; an
+// operand NOT prepacked is packed inline as before.
 struct PackPlan {
   bool packA = false, packB = false;
   std::vector<int> a_axes, b_axes;  // axis orders of the packed layouts
@@ -2549,78 +2171,20 @@ struct PackPlan {
 
 static bool plan_prepack(const Meta& A, const Meta& B, const u64* out_labels,
                          const u64* out_shape, int out_nd, PackPlan* plan,
-                         bool c128 = false) {
-  if (A.nd > TN_MAXR || B.nd > TN_MAXR || out_nd > TN_MAXR) return false;
-  auto find = [](const Meta& t, u64 lab) {
-    for (int i = 0; i < t.nd; ++i)
-      if (t.labels[i] == lab) return i;
-    return -1;
-  };
-  int apos[TN_MAXR], bpos[TN_MAXR];
-  u64 M = 1, N = 1, K = 1;
-  std::vector<int> m_out, n_out;
-  for (int i = 0; i < out_nd; ++i) {
-    apos[i] = find(A, out_labels[i]);
-    bpos[i] = find(B, out_labels[i]);
-    if (apos[i] >= 0 && bpos[i] >= 0) return false;
-    if (apos[i] >= 0) {
-      M *= out_shape[i];
-      m_out.push_back(i);
-    } else if (bpos[i] >= 0) {
-      N *= out_shape[i];
-      n_out.push_back(i);
-    } else {
-      return false;
-    }
-  }
-  std::vector<int> k_a, k_b;
-  for (int i = 0; i < A.nd; ++i) {
-    int j = find(B, A.labels[i]);
-    if (j >= 0) {
-      K *= A.dims[i];
-      k_a.push_back(i);
-      k_b.push_back(j);
-    }
-  }
-  if (M == 1 && N == 1 && K > TN_SMALLK) return false;  // dot route
-  bool skinny = (M < 16 || N < 16);
-  bool gemm_worthy = (K >= 16 && M >= MF_T && N >= MF_TN);
-  bool gather_ok = (K <= TN_SMALLK || skinny);
-  if (gather_ok && !gemm_worthy) return false;  // gather route
-  // steps the gather-staged GEMM will take need no pack at all
-  if (c128 && (M >= 32 && N >= 32) && (M % MF_T == 0) && (N % MF_TN == 0) &&
-      (K % MF_K == 0) && !gather_gemm_disabled()) {
-    bool pow2 = true;
-    for (int i = 0; i < A.nd; ++i)
-      if ((A.dims[i] & (A.dims[i] - 1)) ||
-          (A.dims[i] > 1 && A.strides[i] <= 0))
-        pow2 = false;
-    for (int i = 0; i < B.nd; ++i)
-      if ((B.dims[i] & (B.dims[i] - 1)) ||
-          (B.dims[i] > 1 && B.strides[i] <= 0))
-        pow2 = false;
-    if (pow2) return false;
-  }
-  std::vector<int> a_axes, b_axes;
-  for (int p : m_out) a_axes.push_back(apos[p]);
-  for (int i : k_a) a_axes.push_back(i);
-  for (int j : k_b) b_axes.push_back(j);
-  for (int p : n_out) b_axes.push_back(bpos[p]);
-  auto is_ready = [](const Meta& t, const std::vector<int>& axes) {
-    if ((int)axes.size() != t.nd) return false;
-    i64 stride = 1;
-    for (int i = (int)axes.size() - 1; i >= 0; --i) {
-      if (t.strides[axes[i]] != stride) return false;
-      stride *= (i64)t.dims[axes[i]];
-    }
-    return true;
-  };
-  plan->packA = !is_ready(A, a_axes);
-  plan->packB = !is_ready(B, b_axes);
-  plan->a_axes = std::move(a_axes);
-  plan->b_axes = std::move(b_axes);
-  plan->MK = M * K;
-  plan->KN = K * N;
+                         bool c128) {
+  StepPlan p;
+  std::string err;
+  // (no second stream: the pipeline choice has no bearing on what packs)
+  if (plan_step(c128, out_labels, out_shape, out_nd, A, B, false, &p, &err) !=
+          TN_OK ||
+      p.route != TN_ROUTE_TTGT || p.gather_gemm)
+    return false;
+  plan->packA = p.pack_a;
+  plan->packB = p.pack_b;
+  plan->a_axes.assign(p.a_axes.begin(), p.a_axes.end());
+  plan->b_axes.assign(p.b_axes.begin(), p.b_axes.end());
+  plan->MK = p.m * p.k;
+  plan->KN = p.k * p.n;
   return plan->packA || plan->packB;
 }
 
@@ -2637,15 +2201,6 @@ static void meta_of(const DevTensor& t, Meta* m) {
     stride *= (i64)m->dims[x];
   }
   m->data = t.data;
-}
-
-static bool prepack_disabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("TN_NO_PREPACK");
-    v = (e && e[0] && e[0] != '0') ? 1 : 0;
-  }
-  return v == 1;
 }
 
 static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
@@ -2706,7 +2261,7 @@ static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
   std::vector<hipEvent_t> prep_events;
   ws.events = &prep_events;  // pipeline events: destroyed after the walk
   const bool overlap =
-      !prepack_disabled() && net->stream2 && net->arena.base != nullptr;
+      !env_switch(ENV_NO_PREPACK) && net->stream2 && net->arena.base != nullptr;
 
   for (size_t s = 0; s < nsteps; ++s) {
     u64 i = pairs[2 * s], j = pairs[2 * s + 1];

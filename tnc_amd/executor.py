@@ -19,112 +19,44 @@ from .tensor import CompositeTensor, LeafTensor
 
 class StepInfo:
     __slots__ = ("i", "j", "m", "n", "k", "flops", "out_legs", "out_dims",
-                 "packa", "packb", "pipe_p")
+                 "packa", "packb", "pipe_p", "plan")
 
     def __init__(self, i, j, m, n, k, flops, out_legs, out_dims,
-                 packa=False, packb=False, pipe_p=0):
+                 packa=False, packb=False, pipe_p=0, plan=None):
         self.i, self.j = i, j
         self.m, self.n, self.k = m, n, k
         self.flops = flops
         self.out_legs = out_legs
         self.out_dims = out_dims
-        self.packa = packa  # TTGT would permute A into [M..][K..] order
-        self.packb = packb  # TTGT would permute B into [K..][N..] order
+        self.packa = packa  # A is not already in [M..][K..] order
+        self.packb = packb  # B is not already in [K..][N..] order
         self.pipe_p = pipe_p  # pack-pipeline window count (0 = serial pack)
+        self.plan = plan  # the step's whole hiplib.StepPlan
 
 
-def _pipeline_windows(m, n, k, packa, packb, kdims, esize):
-    """Mirror of the C dispatch's pack-pipeline model (tnc_hip.hip
-    einsum_dev_impl): number of K windows the pipelined TTGT would use,
-    0 when the step packs serially. Keep in sync with the constants there
-    (permute ~4 TB/s, stream ~6 TB/s, window tiles >= 256)."""
-    if not packa:
-        return 0
-    m, n, k = int(m), int(n), int(k)
-    if not (m >= 32 and n >= 32) or m % 128 or n % 64 or k % 16:
-        return 0
-    gemm_worthy = k >= 16 and m >= 128 and n >= 64
-    if (k <= 64 or m < 16 or n < 16) and not gemm_worthy:
-        return 0
-    packbytes = m * k * esize + (k * n * esize if packb else 0)
-    tiles_w = (m // 128) * ((n + 63) // 64)
-    best_save, best_p = 0.0, 0
-    p = 1
-    for d in kdims:
-        if p >= 16:
-            break
-        p *= int(d)
-        if p < 2 or p > 16:
-            continue
-        if (k // p) % 16 or tiles_w < 256:
-            continue
-        save = (2.0 * packbytes / 4e12 * (1 - 1.0 / p)
-                - 2.0 * p * (m * n * esize) / 6e12)
-        if save > best_save:
-            best_save, best_p = save, p
-    # measured gate (see tnc_hip.hip): only strongly-favorable steps win
-    if best_save <= 5e-3 or packbytes < 8.0 * m * n * esize:
-        return 0
-    return best_p
-
-
-def plan_steps(leaves, steps):
+def plan_steps(leaves, steps, dtype="c128"):
     """Host-side metadata walk: per-step (M, N, K), metric flops
-    ((8s-2)*o, contraction_cost.rs:26-32), output legs, and whether the
-    TTGT path would need pack permutes (mirrors einsum_dev_impl's
-    is_ready checks in tnc_amd/csrc/tnc_hip.hip)."""
+    ((8s-2)*o, contraction_cost.rs:26-32), output legs, and how the library
+    will dispatch the step: which operands the TTGT route would pack, the
+    pack-pipeline window count and the workspace it will ask for. All of
+    that comes from tn_plan_step, the planner the dispatch itself runs."""
     views = [LeafTensor(t.legs, t.bond_dims) for t in leaves]
     infos = []
     for i, j in steps:
         a, b = views[i], views[j]
         out = a ^ b
-        shared = a & b
-        m = (a - b).size()
-        n = (b - a).size()
-        k = shared.size()
-        aset, bset = set(a.legs), set(b.legs)
-        shared_a = [l for l in a.legs if l in bset]  # K legs in A order
-        a_axes = [x for x, l in enumerate(a.legs) if l not in bset]
-        a_axes += [a.legs.index(l) for l in shared_a]
-        b_axes = [b.legs.index(l) for l in shared_a]
-        b_axes += [x for x, l in enumerate(b.legs) if l not in aset]
-        packa = a_axes != list(range(len(a.legs)))
-        packb = b_axes != list(range(len(b.legs)))
-        kdims = [a.bond_dims[a.legs.index(l)] for l in shared_a]
-        # window count is esize-invariant (the save model scales linearly)
-        pipe_p = _pipeline_windows(m, n, k, packa, packb, kdims, 16)
+        # the engine always has its second stream
+        p = hiplib.plan_step(out.legs, out.bond_dims, a.legs, a.bond_dims,
+                             b.legs, b.bond_dims, dtype=dtype,
+                             has_stream2=True)
         infos.append(
-            StepInfo(i, j, m, n, k, contract_cost_tensors(a, b), out.legs,
-                     out.bond_dims, packa=packa, packb=packb, pipe_p=pipe_p)
+            StepInfo(i, j, p.m, p.n, p.k, contract_cost_tensors(a, b),
+                     out.legs, out.bond_dims, packa=bool(p.pack_a),
+                     packb=bool(p.pack_b), pipe_p=p.pipe_p, plan=p)
         )
         views[i] = out
         views[j] = None
     return infos
-
-
-def _pack_ws_bytes(info, esize):
-    """Pack-permute workspace of a TTGT step (0 for dot/gather routes)."""
-    gemm_worthy = info.k >= 16 and info.m >= 128 and info.n >= 64
-    if (info.k <= 64 or info.m < 16 or info.n < 16) and not gemm_worthy:
-        return 0
-    ws = 0
-    if info.packa:
-        ws += info.m * info.k * esize
-    if info.packb:
-        ws += info.k * info.n * esize
-    return ws
-
-
-def _step_ws_bytes(info, esize):
-    """Workspace the C dispatch will allocate for one step (mirrors
-    einsum_dev_impl: dot partials, nothing for gather kernels, pack
-    buffers for TTGT). Keep in sync with TN_SMALLK=64, MF_T=128,
-    MF_TN=64 in tnc_amd/csrc/tnc_hip.hip."""
-    if info.m == 1 and info.n == 1 and info.k > 64:
-        return 1 << 25  # dot partial buffer (<= 2^21 blocks * 16 B)
-    # pipelined steps additionally hold pipe_p split-K-style output slices
-    return (_pack_ws_bytes(info, esize)
-            + info.pipe_p * int(info.m) * int(info.n) * esize)
 
 
 def arena_bytes(leaves, steps, infos, esize=16):
@@ -132,14 +64,20 @@ def arena_bytes(leaves, steps, infos, esize=16):
     the workspaces its dispatch actually uses, walked over the plan. The
     pack-overlap executor allocates the NEXT step's pack buffers one step
     early (prepack on stream2), so each step's demand includes them.
-    Padded 15% for fragmentation + split-K slack."""
+    Padded 15% for fragmentation + split-K slack (a split buffer that does
+    not fit only costs the step its split)."""
+    def pack_ws(p):  # pack buffers, or the pipeline's window buffers
+        return p.ws_pack_a + p.ws_pack_b
+
     live = {}  # slot -> bytes (intermediates only; leaves live outside)
     peak = 0
     for s, info in enumerate(infos):
         out_b = info.m * info.n * esize
-        nxt = _pack_ws_bytes(infos[s + 1], esize) if s + 1 < len(infos) else 0
-        demand = (sum(live.values()) + out_b + _step_ws_bytes(info, esize)
-                  + nxt)
+        p = info.plan
+        nxt = pack_ws(infos[s + 1].plan) if s + 1 < len(infos) else 0
+        # dot partials: bounded, not exact (<= 2^21 blocks * 16 B)
+        ws = (1 << 25) if p.ws_dot else pack_ws(p) + p.ws_tmp_c + p.ws_slices
+        demand = sum(live.values()) + out_b + ws + nxt
         peak = max(peak, demand)
         live.pop(info.j, None)
         live[info.i] = out_b
@@ -161,7 +99,7 @@ class ContractionEngine:
         self.leaves = leaves
         self.steps = steps
         self.final = final
-        self.infos = plan_steps(leaves, steps)
+        self.infos = plan_steps(leaves, steps, dtype)
         self.total_flops = sum(s.flops for s in self.infos)
         L = hiplib.lib()
         hiplib.check(L.tn_set_device(device), "tn_set_device")

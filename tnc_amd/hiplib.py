@@ -95,8 +95,62 @@ def lib() -> ctypes.CDLL:
             ctypes.POINTER(ctypes.c_uint64),
         ]
         L.tn_net_destroy.argtypes = [ctypes.c_void_p]
+        L.tn_plan_step.restype = ctypes.c_int
+        L.tn_plan_step.argtypes = [
+            ctypes.c_int, u64p, u64p, ctypes.c_size_t,
+            u64p, u64p, i64p, ctypes.c_size_t,
+            u64p, u64p, i64p, ctypes.c_size_t,
+            ctypes.c_int, ctypes.POINTER(StepPlan),
+        ]
         _lib = L
     return _lib
+
+
+class StepPlan(ctypes.Structure):
+    """tn_step_plan (include/tnc_hip.h): how one einsum step is dispatched."""
+
+    _fields_ = [
+        ("m", ctypes.c_uint64), ("n", ctypes.c_uint64), ("k", ctypes.c_uint64),
+        ("route", ctypes.c_int32), ("kind", ctypes.c_int32),
+        ("dot_form", ctypes.c_int32), ("tbits", ctypes.c_int32),
+        ("dot_blocks", ctypes.c_uint64),
+        ("gather_ok", ctypes.c_int32),
+        ("pack_a", ctypes.c_int32), ("pack_b", ctypes.c_int32),
+        ("direct", ctypes.c_int32), ("gather_gemm", ctypes.c_int32),
+        ("pipe_p", ctypes.c_int32), ("pipe_npre", ctypes.c_int32),
+        ("pipe_kc", ctypes.c_uint64),
+        ("row_tiles", ctypes.c_uint64), ("col_tiles", ctypes.c_uint64),
+        ("splitk", ctypes.c_uint64), ("kchunk", ctypes.c_uint64),
+        ("kernel", ctypes.c_int32),
+        ("ws_pack_a", ctypes.c_uint64), ("ws_pack_b", ctypes.c_uint64),
+        ("ws_tmp_c", ctypes.c_uint64), ("ws_slices", ctypes.c_uint64),
+        ("ws_split", ctypes.c_uint64), ("ws_dot", ctypes.c_uint64),
+    ]
+
+
+ROUTE_DOT, ROUTE_GATHER, ROUTE_TTGT = 0, 1, 2
+DOT_LINEAR, DOT_TILED, DOT_GATHER = 0, 1, 2
+(GEMM_V1, GEMM_MFMA, GEMM_C128_GLDS, GEMM_C128_PURE, GEMM_C128_3M,
+ GEMM_C128_GATHER, GEMM_C64_PURE) = range(7)
+
+
+def plan_step(out_labels, out_shape, a_labels, a_shape, b_labels, b_shape,
+              dtype="c128", has_stream2=False, a_strides=None,
+              b_strides=None) -> StepPlan:
+    """The dispatch plan of one einsum step (tn_plan_step). Strides are in
+    elements; None = contiguous row-major. Needs no GPU."""
+    plan = StepPlan()
+    rc = lib().tn_plan_step(
+        {"c128": 0, "c64": 1}[dtype],
+        _u64arr(out_labels), _u64arr(out_shape), len(out_labels),
+        _u64arr(a_labels), _u64arr(a_shape),
+        None if a_strides is None else _i64arr(a_strides), len(a_labels),
+        _u64arr(b_labels), _u64arr(b_shape),
+        None if b_strides is None else _i64arr(b_strides), len(b_labels),
+        int(has_stream2), ctypes.byref(plan),
+    )
+    check(rc, "tn_plan_step")
+    return plan
 
 
 def last_error() -> str:
