@@ -131,6 +131,9 @@ typedef struct tn_step_plan {
   /* workspace bytes the step will ask for. A pipelined step holds its window
    * buffers in ws_pack_a / ws_pack_b and has no split buffer. */
   uint64_t ws_pack_a, ws_pack_b, ws_tmp_c, ws_slices, ws_split, ws_dot;
+  /* a non-direct out order is stored by the GEMM's scatter epilogue: no
+   * temporary C (ws_tmp_c == 0), no out permute (kind 2) */
+  int32_t scatter_out;
 } tn_step_plan;
 
 /* Plan the step tn_einsum_*_dev would run on these operands (dtype 0 =
@@ -145,6 +148,20 @@ int tn_plan_step(int dtype, const uint64_t* out_labels,
                  const uint64_t* b_labels, const uint64_t* b_shape,
                  const int64_t* b_strides, size_t b_ndim, int has_stream2,
                  tn_step_plan* plan);
+
+/* The layout pre-pass the network executor runs before its walk: for a flat
+ * replace-left path over leaves given as concatenated labels/dims (leaf_nd
+ * entries each), decide the order every step stores its output in. A step
+ * whose consumer would pack that output stores it in the consumer's operand
+ * layout instead, when the scatter epilogue can write it (scatter_out[s] =
+ * 1). inline_pack_bytes[s] is what step s still packs inline, on the main
+ * stream: operands that are not in GEMM layout and could not be prepacked
+ * during the previous step because that step produces them. Either output
+ * may be NULL. Needs no GPU; honours TN_EPI_SCATTER. */
+int tn_plan_layouts(int dtype, const uint64_t* leaf_labels,
+                    const uint64_t* leaf_dims, const uint64_t* leaf_nd,
+                    size_t nleaves, const uint64_t* pairs, size_t nsteps,
+                    int32_t* scatter_out, uint64_t* inline_pack_bytes);
 
 /* ------------ network executor (contract_tensor_network) ------------- */
 

@@ -61,6 +61,16 @@ struct GatherGemmMap {
   u64 kstride[34];    // source stride contributed by k bit b
 };
 
+// Scatter epilogue: C(row, col) is stored at out[R(row) + Cc(col)]. With
+// every out dim a power of two each destination index bit comes from one row
+// bit or one column bit, so the offset is separable.
+#define TN_SCATTER_MINRUN 3  // low column bits that must stay in place
+struct ScatterMap {
+  int rbits, cbits;   // bits of the row (M) and column (N) index
+  u64 rstride[34];    // destination stride (elements) of row bit b
+  u64 cstride[34];    // destination stride of column bit b
+};
+
 struct Meta {
   int nd;
   u64 labels[TN_MAXR];
@@ -106,20 +116,26 @@ struct AxisList {
 //                     hold, gate ignored (tests; also lets split-K slices
 //                     run through it, which the default never does)
 //   TN_NO_PREPACK     set: no look-ahead pack of the next step's operands
+//   TN_EPI_SCATTER    unset: the 3M GEMM may store its output through the
+//                     scatter epilogue, and plan_layouts may choose a step's
+//                     stored order for its consumer; "0": neither (every
+//                     step stores the symmetric-difference order)
 enum EnvSwitch { ENV_NO_PIPELINE, ENV_PIPELINE_FORCE, ENV_GATHER_GEMM,
-                 ENV_GEMM3M, ENV_NO_PREPACK, ENV_COUNT };
+                 ENV_GEMM3M, ENV_NO_PREPACK, ENV_EPI_SCATTER, ENV_COUNT };
 enum { GEMM3M_OFF = 0, GEMM3M_GATED = 1, GEMM3M_FORCE = 2 };
 
 inline int env_switch(EnvSwitch s) {
   static const char* const names[ENV_COUNT] = {
       "TN_NO_PIPELINE", "TN_PIPELINE_FORCE", "TN_GATHER_GEMM", "TN_GEMM3M",
-      "TN_NO_PREPACK"};
-  static int cache[ENV_COUNT] = {-1, -1, -1, -1, -1};
+      "TN_NO_PREPACK", "TN_EPI_SCATTER"};
+  static int cache[ENV_COUNT] = {-1, -1, -1, -1, -1, -1};
   int& v = cache[s];
   if (v < 0) {
     const char* e = getenv(names[s]);
     const bool on = e && e[0] && e[0] != '0';
-    if (s != ENV_GEMM3M)
+    if (s == ENV_EPI_SCATTER)
+      v = (!e || !e[0] || on) ? 1 : 0;  // on unless "0"
+    else if (s != ENV_GEMM3M)
       v = on ? 1 : 0;
     else if (!e || !e[0])
       v = GEMM3M_GATED;
@@ -140,6 +156,7 @@ struct StepPlan : tn_step_plan {
   AxisList a_axes, b_axes;
   DotPerm dp;              // dot route, tiled form
   GatherGemmMap gmA{}, gmB{};  // TTGT route, gather_gemm
+  ScatterMap smap{};           // TTGT route, scatter_out
   u64 nout() const { return m * n; }
 };
 
@@ -227,6 +244,40 @@ inline bool build_ggmap(const Meta& t, const int* axes_r, int nr,
   };
   return fill(axes_r, nr, m->rstride, &m->rbits) &&
          fill(axes_k, nk, m->kstride, &m->kbits);
+}
+
+// Destination strides of the GEMM's row and column bits when C = [M legs in
+// out order][N legs in out order] is stored straight into `out` (row-major
+// in out order). Returns the run length r: the number of lowest destination
+// bits that are, in order, the lowest column bits (2^r consecutive columns
+// land contiguously), or -1 when a dim is no power of two or the bits do not
+// fit the map.
+inline int build_scatter_map(const u64* out_shape, int out_nd,
+                             const AxisList& m_out, const AxisList& n_out,
+                             ScatterMap* sm) {
+  u64 ostride[TN_MAXR];
+  u64 stride = 1;
+  for (int i = out_nd - 1; i >= 0; --i) {
+    if (out_shape[i] & (out_shape[i] - 1)) return -1;
+    ostride[i] = stride;
+    stride *= out_shape[i];
+  }
+  auto fill = [&](const AxisList& axes, u64* dst, int* nbits) {
+    int nb = 0;
+    for (int t = axes.n - 1; t >= 0; --t)
+      for (u64 v = 1; v < out_shape[axes[t]]; v <<= 1) {
+        if (nb >= 34) return false;
+        dst[nb++] = ostride[axes[t]] * v;
+      }
+    *nbits = nb;
+    return true;
+  };
+  if (!fill(m_out, sm->rstride, &sm->rbits) ||
+      !fill(n_out, sm->cstride, &sm->cbits))
+    return -1;
+  int r = 0;
+  while (r < sm->cbits && sm->cstride[r] == (1ull << r)) ++r;
+  return r;
 }
 
 // Structural preconditions of k_zgemm_c128_glds_3m beyond purity: its
@@ -491,15 +542,216 @@ inline int plan_step(bool c128, const u64* out_labels, const u64* out_shape,
                       : pure ? TN_GEMM_C128_PURE : TN_GEMM_C128_GLDS;
   }
 
+  // scatter epilogue: a non-direct out order is written by the 3M GEMM
+  // itself, no temporary C and no unpack permute. The run-length gate
+  // (TN_SCATTER_MINRUN low column bits in place = 128 contiguous bytes per 8
+  // columns) is the smallest store run the GEMM's epilogue is known to
+  // sustain at full rate.
+  if (!p.direct && c128 && p.kernel == TN_GEMM_C128_3M && p.splitk == 1 &&
+      !p.pipe_p && !p.gather_gemm && env_switch(ENV_EPI_SCATTER) &&
+      build_scatter_map(out_shape, out_nd, p.m_out, p.n_out, &p.smap) >=
+          TN_SCATTER_MINRUN) {
+    p.scatter_out = 1;
+    p.kind = 2;  // no out permute runs
+  }
+
   // workspace the step will ask for (a pipelined step's pack buffers hold
   // all P windows back to back)
   const bool packs = p.pipe_p || !p.gather_gemm;
-  p.ws_tmp_c = p.direct ? 0 : nout * esize;
+  p.ws_tmp_c = (p.direct || p.scatter_out) ? 0 : nout * esize;
   p.ws_pack_a = (packs && p.pack_a) ? M * K * esize : 0;
   p.ws_pack_b = (packs && p.pack_b) ? K * N * esize : 0;
   p.ws_slices = (u64)p.pipe_p * nout * esize;
   p.ws_split = (!p.pipe_p && p.splitk > 1) ? p.splitk * nout * esize : 0;
   return TN_OK;
+}
+
+// ---- layout pre-pass ------------------------------------------------------
+// Decides, for a whole flat replace-left path, the order each step stores
+// its output in. Today's rule is the symmetric difference of the operands'
+// stored orders. When the next step c = s+1 reads step s's output as its A
+// operand and would have to pack it inline (the one operand the prepack
+// cannot hide: it does not exist while step s-1 runs), step s stores
+//   [M' legs][K' legs]      M' = legs c keeps, K' = legs c contracts
+// instead, provided plan_step admits that order to the scatter epilogue.
+// Inside the K' group legs that come from M_s go first and legs from N_s
+// last, so the N_s legs of K' are both the lowest column bits of step s's
+// GEMM and the lowest destination bits: the run length the gate asks for.
+// The M' group is free as far as step s goes; it takes the order step c
+// wants its own rows in, so that c finds the operand ready whatever c's
+// own stored order turns out to be. That makes the proposals depend on later
+// steps only: one backward sweep over label sets proposes, one forward sweep
+// over the stored orders decides (gate on the real operands, would-pack test
+// on c, and no proposal that makes step s pack more inline than c saves).
+// An output read as a B operand is left alone: its K' order is dictated by
+// the other operand. The last step stores today's order, so results keep
+// their legs. Slot labels always are the stored order.
+
+struct LayoutTensor {
+  std::vector<u64> labels, dims;
+};
+
+struct LayoutPlan {
+  bool valid = false;  // false: the walk uses the symmetric difference
+  std::vector<LayoutTensor> out;  // stored order of every step's output
+  std::vector<int32_t> scatter_out;
+  std::vector<u64> inline_pack_bytes;
+};
+
+inline bool layout_has(const LayoutTensor& t, u64 lab) {
+  for (u64 l : t.labels)
+    if (l == lab) return true;
+  return false;
+}
+
+// A-only legs in A order, then B-only legs in B order
+inline void layout_symdiff(const LayoutTensor& a, const LayoutTensor& b,
+                           LayoutTensor* out) {
+  out->labels.clear();
+  out->dims.clear();
+  for (size_t x = 0; x < a.labels.size(); ++x)
+    if (!layout_has(b, a.labels[x])) {
+      out->labels.push_back(a.labels[x]);
+      out->dims.push_back(a.dims[x]);
+    }
+  for (size_t x = 0; x < b.labels.size(); ++x)
+    if (!layout_has(a, b.labels[x])) {
+      out->labels.push_back(b.labels[x]);
+      out->dims.push_back(b.dims[x]);
+    }
+}
+
+inline void layout_meta(const LayoutTensor& t, Meta* m) {
+  m->nd = (int)t.labels.size();
+  i64 stride = 1;
+  for (int x = m->nd - 1; x >= 0; --x) {
+    m->labels[x] = t.labels[x];
+    m->dims[x] = t.dims[x];
+    m->strides[x] = stride;
+    stride *= (i64)t.dims[x];
+  }
+  m->data = nullptr;
+}
+
+inline bool layout_plan_step(bool c128, const LayoutTensor& out,
+                             const LayoutTensor& a, const LayoutTensor& b,
+                             bool has_stream2, StepPlan* p) {
+  Meta ma, mb;
+  std::string err;
+  layout_meta(a, &ma);
+  layout_meta(b, &mb);
+  return plan_step(c128, out.labels.data(), out.dims.data(),
+                   (int)out.labels.size(), ma, mb, has_stream2, p,
+                   &err) == TN_OK;
+}
+
+inline void plan_layouts(bool c128, const std::vector<LayoutTensor>& leaves,
+                         const u64* pairs, size_t nsteps, LayoutPlan* lp) {
+  *lp = LayoutPlan();
+  const size_t n = leaves.size();
+  const u64 esize = c128 ? 16 : 8;
+  // canonical walk: today's orders. Supplies the label sets of every step
+  // and which step consumes each output.
+  std::vector<LayoutTensor> canon(leaves), can_a(nsteps), can_b(nsteps),
+      can_out(nsteps);
+  std::vector<char> alive(n, 1);
+  std::vector<long> producer(n, -1), consumer(nsteps, -1);
+  std::vector<char> cons_as_a(nsteps, 0);
+  for (const LayoutTensor& t : leaves)
+    if (t.labels.size() > (size_t)TN_MAXR) return;
+  for (size_t s = 0; s < nsteps; ++s) {
+    const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
+    if (i >= n || j >= n || i == j || !alive[i] || !alive[j]) return;
+    can_a[s] = canon[i];
+    can_b[s] = canon[j];
+    layout_symdiff(canon[i], canon[j], &can_out[s]);
+    if (can_out[s].labels.size() > (size_t)TN_MAXR) return;
+    if (producer[i] >= 0) {
+      consumer[producer[i]] = (long)s;
+      cons_as_a[producer[i]] = 1;
+    }
+    if (producer[j] >= 0) consumer[producer[j]] = (long)s;
+    canon[i] = can_out[s];
+    producer[i] = (long)s;
+    alive[j] = 0;
+  }
+
+  // backward sweep: proposals
+  std::vector<LayoutTensor> want(nsteps);
+  const bool enabled = c128 && env_switch(ENV_EPI_SCATTER);
+  for (size_t s = nsteps; enabled && s-- > 0;) {
+    const long c = consumer[s];
+    if (c != (long)s + 1 || !cons_as_a[s]) continue;
+    const LayoutTensor& other = can_b[c];
+    // the order step c wants its rows (= M' legs) in
+    const LayoutTensor& row_src = want[c].labels.empty() ? can_out[s] : want[c];
+    LayoutTensor d;
+    for (size_t x = 0; x < row_src.labels.size(); ++x)
+      if (layout_has(can_out[s], row_src.labels[x]) &&
+          !layout_has(other, row_src.labels[x])) {
+        d.labels.push_back(row_src.labels[x]);
+        d.dims.push_back(row_src.dims[x]);
+      }
+    const size_t nrows = d.labels.size();
+    for (size_t x = 0; x < can_out[s].labels.size(); ++x)
+      if (layout_has(other, can_out[s].labels[x])) {
+        d.labels.push_back(can_out[s].labels[x]);
+        d.dims.push_back(can_out[s].dims[x]);
+      }
+    if (nrows == 0 || nrows == d.labels.size()) continue;
+    StepPlan p;
+    if (layout_plan_step(c128, d, can_a[s], can_b[s], false, &p) &&
+        p.scatter_out)
+      want[s] = d;
+  }
+
+  // forward sweep: decisions, on the stored orders
+  std::vector<LayoutTensor> stored(leaves);
+  lp->out.resize(nsteps);
+  lp->scatter_out.assign(nsteps, 0);
+  lp->inline_pack_bytes.assign(nsteps, 0);
+  auto inline_bytes = [&](size_t s, const StepPlan& p) -> u64 {
+    if (p.route != TN_ROUTE_TTGT || p.gather_gemm) return 0;
+    // an operand the previous step produced cannot have been prepacked
+    const bool a_new = s == 0 || pairs[2 * s] == pairs[2 * (s - 1)];
+    const bool b_new = s == 0 || pairs[2 * s + 1] == pairs[2 * (s - 1)];
+    return ((p.pack_a && a_new) ? p.m * p.k * esize : 0) +
+           ((p.pack_b && b_new) ? p.k * p.n * esize : 0);
+  };
+  for (size_t s = 0; s < nsteps; ++s) {
+    const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
+    const LayoutTensor &A = stored[i], &B = stored[j];
+    LayoutTensor base;
+    layout_symdiff(A, B, &base);
+    StepPlan pb;
+    if (!layout_plan_step(c128, base, A, B, true, &pb)) return;
+    LayoutTensor chosen = consumer[s] < 0 ? can_out[s] : base;
+    StepPlan pc = pb;
+    if (consumer[s] < 0 && chosen.labels != base.labels &&
+        !layout_plan_step(c128, chosen, A, B, true, &pc))
+      return;
+    if (!want[s].labels.empty()) {
+      // would step s+1 pack this output inline under today's order?
+      const u64 oj = pairs[2 * (s + 1) + 1];
+      LayoutTensor next_out;
+      layout_symdiff(base, stored[oj], &next_out);
+      StepPlan pn, pw;
+      const bool packs_next =
+          layout_plan_step(c128, next_out, base, stored[oj], true, &pn) &&
+          pn.route == TN_ROUTE_TTGT && !pn.gather_gemm && pn.pack_a;
+      if (packs_next && layout_plan_step(c128, want[s], A, B, true, &pw) &&
+          pw.scatter_out &&
+          inline_bytes(s, pw) < inline_bytes(s, pb) + pn.m * pn.k * esize) {
+        chosen = want[s];
+        pc = pw;
+      }
+    }
+    lp->scatter_out[s] = pc.scatter_out;
+    lp->inline_pack_bytes[s] = inline_bytes(s, pc);
+    lp->out[s] = chosen;
+    stored[i] = chosen;
+  }
+  lp->valid = true;
 }
 
 #endif  // TNC_STEP_PLAN_HPP

@@ -829,12 +829,17 @@ __global__ __launch_bounds__(MF_THREADS) void k_zgemm_c128_glds_pure(
 // launcher must guarantee MF_T*K*16 and MF_K*N*16 fit in 32 bits, on top of
 // the pure-shape conditions (M % 128 == 0, N % 64 == 0, K-slices whole
 // 16-tiles). No guarded branch in the loop.
+// SCATTER selects the epilogue only; the main loop is shared. The scatter
+// epilogue stores C(row, col) at C[R(row) + Cc(col)] (ScatterMap,
+// step_plan.hpp): a wave-uniform part from the tile origin plus a tile-local
+// part from a 128-entry row table and a 64-entry column table, built in LDS
+// over As once the main loop is done. Offsets are 64-bit throughout.
 #define MF3_THREADS 256
-__global__ __launch_bounds__(MF3_THREADS)
-__attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m(
+template <bool SCATTER>
+__device__ __forceinline__ void zgemm_c128_3m_body(
     const double2* __restrict__ A, const double2* __restrict__ B,
     double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
-    unsigned tiles, u64 kchunk) {
+    unsigned tiles, u64 kchunk, const ScatterMap* sm) {
   constexpr int TM = MF_T, TN = MF_TN, KT = MF_K;
   constexpr int WN = 2, FM = 4, FN = 2;
   constexpr int APIECES = TM * KT / MF3_THREADS;  // 8 glds per wave
@@ -908,15 +913,65 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m(
     __syncthreads();
   }
   const int ccol = lane % 16;
-  for (int i = 0; i < FM; ++i)
-    for (int j = 0; j < FN; ++j)
-      for (int r = 0; r < 4; ++r) {
-        u64 row = brow + (wm * FM + i) * 16 + (lane / 16) + 4 * r;
-        u64 col = bcol + (wn * FN + j) * 16 + ccol;
-        C[row * N + col] = make_double2(
-            p1[i][j][r] - p2[i][j][r],
-            (p3[i][j][r] - p1[i][j][r]) - p2[i][j][r]);
+  if constexpr (SCATTER) {
+    // the loop's closing barrier has retired every read of As
+    u64* rowtab = (u64*)As;
+    u64* coltab = rowtab + TM;
+    const int t = threadIdx.x;
+    if (t < TM + TN) {
+      const bool isrow = t < TM;
+      const int idx = isrow ? t : t - TM;
+      const int nb = isrow ? 7 : 6;  // log2(TM), log2(TN)
+      u64 off = 0;
+      for (int b = 0; b < nb; ++b)
+        if ((idx >> b) & 1) off += isrow ? sm->rstride[b] : sm->cstride[b];
+      rowtab[t] = off;  // coltab follows rowtab
+    }
+    u64 base = 0;  // wave-uniform: the tile origin's destination offset
+    for (int b = 7; b < sm->rbits; ++b)
+      if ((brow >> b) & 1) base += sm->rstride[b];
+    for (int b = 6; b < sm->cbits; ++b)
+      if ((bcol >> b) & 1) base += sm->cstride[b];
+    __syncthreads();
+    for (int i = 0; i < FM; ++i)
+      for (int j = 0; j < FN; ++j) {
+        const u64 coff = base + coltab[(wn * FN + j) * 16 + ccol];
+        for (int r = 0; r < 4; ++r) {
+          const u64 roff = rowtab[(wm * FM + i) * 16 + (lane / 16) + 4 * r];
+          C[roff + coff] = make_double2(
+              p1[i][j][r] - p2[i][j][r],
+              (p3[i][j][r] - p1[i][j][r]) - p2[i][j][r]);
+        }
       }
+  } else {
+    for (int i = 0; i < FM; ++i)
+      for (int j = 0; j < FN; ++j)
+        for (int r = 0; r < 4; ++r) {
+          u64 row = brow + (wm * FM + i) * 16 + (lane / 16) + 4 * r;
+          u64 col = bcol + (wn * FN + j) * 16 + ccol;
+          C[row * N + col] = make_double2(
+              p1[i][j][r] - p2[i][j][r],
+              (p3[i][j][r] - p1[i][j][r]) - p2[i][j][r]);
+        }
+  }
+}
+
+__global__ __launch_bounds__(MF3_THREADS)
+__attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
+    unsigned tiles, u64 kchunk) {
+  zgemm_c128_3m_body<false>(A, B, C, M, N, K, col_tiles, tiles, kchunk,
+                            nullptr);
+}
+
+// Launched unsplit only (tiles == grid): the map covers one M x N output.
+__global__ __launch_bounds__(MF3_THREADS)
+__attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m_scatter(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
+    unsigned tiles, u64 kchunk, ScatterMap sm) {
+  zgemm_c128_3m_body<true>(A, B, C, M, N, K, col_tiles, tiles, kchunk, &sm);
 }
 
 
@@ -1706,6 +1761,9 @@ static int ttgt_serial(const Step<CT>& s, CT* Cg, WsBlock<CT>& packA,
     if (p.kernel == TN_GEMM_C128_GATHER)
       k_zgemm_c128_glds_gather<<<grid, MF_THREADS, 0, s.stream>>>(
           s.Adata, s.Bdata, gemm_out, M, N, K, ct, nt, kchunk, p.gmA, p.gmB);
+    else if (p.kernel == TN_GEMM_C128_3M && p.scatter_out)
+      k_zgemm_c128_glds_3m_scatter<<<grid, MF3_THREADS, 0, s.stream>>>(
+          Ag, Bg, gemm_out, M, N, K, ct, nt, kchunk, p.smap);
     else if (p.kernel == TN_GEMM_C128_3M)
       k_zgemm_c128_glds_3m<<<grid, MF3_THREADS, 0, s.stream>>>(
           Ag, Bg, gemm_out, M, N, K, ct, nt, kchunk);
@@ -1745,7 +1803,10 @@ static int run_ttgt(const Step<CT>& s) {
   WsBlock<CT> tmpC(s.ws), packB(s.ws), packA(s.ws);
   CT* Cg = s.out;
   int rc_ = TN_OK;
-  if (!p.direct) {
+  // (a scatter_out step is never pipelined or split: its GEMM stores
+  // straight into out, in out order)
+  const bool to_out = p.direct || p.scatter_out;
+  if (!to_out) {
     rc_ = tmpC.alloc(p.nout() * sizeof(CT));
     Cg = tmpC.p;
   }
@@ -1755,7 +1816,7 @@ static int run_ttgt(const Step<CT>& s) {
   // the temporary C or a pack buffer doesn't fit -> run the shape through
   // the (slower) gather kernels instead of failing the whole contraction
   if (rc_ == TN_ERR_OOM && p.gather_ok) return run_gather(s);
-  if (rc_ || p.direct) return rc_;
+  if (rc_ || to_out) return rc_;
   // permute tmp [M legs (out order)][N legs (out order)] -> out order;
   // source strides of each out axis inside tmp:
   std::vector<i64> tmp_stride(s.out_nd, 0);
@@ -1913,6 +1974,31 @@ extern "C" int tn_plan_step(int dtype, const u64* out_labels,
   return TN_OK;
 }
 
+extern "C" int tn_plan_layouts(int dtype, const u64* leaf_labels,
+                               const u64* leaf_dims, const u64* leaf_nd,
+                               size_t nleaves, const u64* pairs, size_t nsteps,
+                               int32_t* scatter_out, u64* inline_pack_bytes) {
+  if ((dtype != 0 && dtype != 1) || (nleaves && !leaf_nd) ||
+      (nsteps && !pairs))
+    FAILV(TN_ERR_INVALID, "unknown dtype or null leaves/pairs");
+  std::vector<LayoutTensor> lt(nleaves);
+  size_t at = 0;
+  for (size_t x = 0; x < nleaves; ++x) {
+    lt[x].labels.assign(leaf_labels + at, leaf_labels + at + leaf_nd[x]);
+    lt[x].dims.assign(leaf_dims + at, leaf_dims + at + leaf_nd[x]);
+    at += leaf_nd[x];
+  }
+  LayoutPlan lp;
+  plan_layouts(dtype == 0, lt, pairs, nsteps, &lp);
+  if (!lp.valid)
+    FAILV(TN_ERR_INVALID, "invalid contraction path or rank over %d", TN_MAXR);
+  for (size_t s = 0; s < nsteps; ++s) {
+    if (scatter_out) scatter_out[s] = lp.scatter_out[s];
+    if (inline_pack_bytes) inline_pack_bytes[s] = lp.inline_pack_bytes[s];
+  }
+  return TN_OK;
+}
+
 static u64 span_elems(const u64* shape, const i64* strides, size_t nd) {
   // max linear offset + 1, assuming nonnegative strides
   u64 span = 1;
@@ -2025,6 +2111,10 @@ struct tn_net {
   // reserved). Invalidated by a different path or new leaves.
   hipGraphExec_t graph_exec = nullptr;
   std::vector<u64> graph_pairs;
+  // stored out order of every step (plan_layouts), kept per path
+  LayoutPlan layout;
+  std::vector<u64> layout_pairs;
+  bool layout_known = false;
   int graph_state = 0;  // 0 = no normal run yet, 1 = ready to capture,
                         // 2 = captured, -1 = disabled (spill/failure)
 
@@ -2033,6 +2123,7 @@ struct tn_net {
     graph_exec = nullptr;
     graph_pairs.clear();
     if (graph_state > 0) graph_state = 0;
+    layout_known = false;  // same triggers: the network or the arena changed
   }
 };
 
@@ -2132,7 +2223,8 @@ extern "C" int64_t tn_net_add_leaf_dev(tn_net* net, const u64* labels,
 }
 
 // out legs of one step = symmetric difference, A-only legs in A order then
-// B-only in B order (tensor.rs:709-725) — the executor's layout contract.
+// B-only in B order (tensor.rs:709-725) — the executor's layout contract
+// wherever the layout pre-pass (plan_layouts) has not chosen another order.
 static void symdiff(const DevTensor& a, const DevTensor& b,
                     std::vector<u64>* labels, std::vector<u64>* dims) {
   for (size_t i = 0; i < a.labels.size(); ++i) {
@@ -2263,6 +2355,31 @@ static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
   const bool overlap =
       !env_switch(ENV_NO_PREPACK) && net->stream2 && net->arena.base != nullptr;
 
+  // stored order of every step's output, decided once per path
+  if (!net->layout_known || net->layout_pairs.size() != 2 * nsteps ||
+      !std::equal(net->layout_pairs.begin(), net->layout_pairs.end(), pairs)) {
+    std::vector<LayoutTensor> lt(n);
+    for (size_t x = 0; x < n; ++x) {
+      lt[x].labels = net->leaves[x].labels;
+      lt[x].dims = net->leaves[x].dims;
+    }
+    plan_layouts(net->dtype == 0, lt, pairs, nsteps, &net->layout);
+    net->layout_pairs.assign(pairs, pairs + 2 * nsteps);
+    net->layout_known = true;
+  }
+  const LayoutPlan& layout = net->layout;
+  // out legs of step s with operands a, b (an invalid path has no plan; the
+  // walk reports it)
+  auto out_order = [&](size_t s, const DevTensor& a, const DevTensor& b,
+                       std::vector<u64>* labels, std::vector<u64>* dims) {
+    if (layout.valid) {
+      *labels = layout.out[s].labels;
+      *dims = layout.out[s].dims;
+    } else {
+      symdiff(a, b, labels, dims);
+    }
+  };
+
   for (size_t s = 0; s < nsteps; ++s) {
     u64 i = pairs[2 * s], j = pairs[2 * s + 1];
     if (i >= n || j >= n || !alive[i] || !alive[j] || i == j) {
@@ -2288,7 +2405,7 @@ static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
     DevTensor& A = slots[i];
     DevTensor& B = slots[j];
     DevTensor out;
-    symdiff(A, B, &out.labels, &out.dims);
+    out_order(s, A, B, &out.labels, &out.dims);
     out.elems = 1;
     for (u64 d : out.dims) out.elems *= d;
     if (ws_alloc(ws, (void**)&out.data, out.elems * net->esize) != TN_OK) {
@@ -2311,7 +2428,7 @@ static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
         const DevTensor& TA = (ni == i) ? out : slots[ni];
         const DevTensor& TB = (nj == i) ? out : slots[nj];
         std::vector<u64> nlabels, ndims;
-        symdiff(TA, TB, &nlabels, &ndims);
+        out_order(s + 1, TA, TB, &nlabels, &ndims);
         Meta mna, mnb;
         PackPlan plan;
         if ((int)TA.labels.size() <= TN_MAXR &&

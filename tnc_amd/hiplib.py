@@ -102,6 +102,12 @@ def lib() -> ctypes.CDLL:
             u64p, u64p, i64p, ctypes.c_size_t,
             ctypes.c_int, ctypes.POINTER(StepPlan),
         ]
+        L.tn_plan_layouts.restype = ctypes.c_int
+        L.tn_plan_layouts.argtypes = [
+            ctypes.c_int, u64p, u64p, u64p, ctypes.c_size_t,
+            u64p, ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_int32), u64p,
+        ]
         _lib = L
     return _lib
 
@@ -125,6 +131,7 @@ class StepPlan(ctypes.Structure):
         ("ws_pack_a", ctypes.c_uint64), ("ws_pack_b", ctypes.c_uint64),
         ("ws_tmp_c", ctypes.c_uint64), ("ws_slices", ctypes.c_uint64),
         ("ws_split", ctypes.c_uint64), ("ws_dot", ctypes.c_uint64),
+        ("scatter_out", ctypes.c_int32),
     ]
 
 
@@ -151,6 +158,26 @@ def plan_step(out_labels, out_shape, a_labels, a_shape, b_labels, b_shape,
     )
     check(rc, "tn_plan_step")
     return plan
+
+
+def plan_layouts(leaves, steps, dtype="c128"):
+    """The executor's layout pre-pass (tn_plan_layouts) over a flat
+    replace-left path. leaves = [(labels, dims), ...], steps = [(i, j), ...].
+    Returns (scatter_out[], inline_pack_bytes[]), one entry per step: whether
+    the step stores its output through the scatter epilogue, and the bytes
+    it still packs inline on the main stream. Needs no GPU."""
+    n = len(steps)
+    scatter = (ctypes.c_int32 * n)()
+    inline = (ctypes.c_uint64 * n)()
+    rc = lib().tn_plan_layouts(
+        {"c128": 0, "c64": 1}[dtype],
+        _u64arr([l for labels, _ in leaves for l in labels]),
+        _u64arr([d for _, dims in leaves for d in dims]),
+        _u64arr([len(labels) for labels, _ in leaves]), len(leaves),
+        _u64arr([x for p in steps for x in p]), n, scatter, inline,
+    )
+    check(rc, "tn_plan_layouts")
+    return list(scatter), list(inline)
 
 
 def last_error() -> str:
