@@ -134,6 +134,8 @@ typedef struct tn_step_plan {
   /* a non-direct out order is stored by the GEMM's scatter epilogue: no
    * temporary C (ws_tmp_c == 0), no out permute (kind 2) */
   int32_t scatter_out;
+  /* the 3M kernel runs its pipelined main loop (TN_GEMM3M_PIPE) */
+  int32_t gemm_pipe;
 } tn_step_plan;
 
 /* Plan the step tn_einsum_*_dev would run on these operands (dtype 0 =

@@ -115,25 +115,30 @@ struct AxisList {
 //                     "force": wherever the kernel's structural preconditions
 //                     hold, gate ignored (tests; also lets split-K slices
 //                     run through it, which the default never does)
+//   TN_GEMM3M_PIPE    unset: the 3M kernel runs its pipelined main loop
+//                     (operand staging of the next K-slab under the MFMAs of
+//                     this one); "0": the serial loop (stage, barrier, MFMAs,
+//                     barrier), same binary, bit-identical results
 //   TN_NO_PREPACK     set: no look-ahead pack of the next step's operands
 //   TN_EPI_SCATTER    unset: the 3M GEMM may store its output through the
 //                     scatter epilogue, and plan_layouts may choose a step's
 //                     stored order for its consumer; "0": neither (every
 //                     step stores the symmetric-difference order)
 enum EnvSwitch { ENV_NO_PIPELINE, ENV_PIPELINE_FORCE, ENV_GATHER_GEMM,
-                 ENV_GEMM3M, ENV_NO_PREPACK, ENV_EPI_SCATTER, ENV_COUNT };
+                 ENV_GEMM3M, ENV_NO_PREPACK, ENV_EPI_SCATTER, ENV_GEMM3M_PIPE,
+                 ENV_COUNT };
 enum { GEMM3M_OFF = 0, GEMM3M_GATED = 1, GEMM3M_FORCE = 2 };
 
 inline int env_switch(EnvSwitch s) {
   static const char* const names[ENV_COUNT] = {
       "TN_NO_PIPELINE", "TN_PIPELINE_FORCE", "TN_GATHER_GEMM", "TN_GEMM3M",
-      "TN_NO_PREPACK", "TN_EPI_SCATTER"};
-  static int cache[ENV_COUNT] = {-1, -1, -1, -1, -1, -1};
+      "TN_NO_PREPACK", "TN_EPI_SCATTER", "TN_GEMM3M_PIPE"};
+  static int cache[ENV_COUNT] = {-1, -1, -1, -1, -1, -1, -1};
   int& v = cache[s];
   if (v < 0) {
     const char* e = getenv(names[s]);
     const bool on = e && e[0] && e[0] != '0';
-    if (s == ENV_EPI_SCATTER)
+    if (s == ENV_EPI_SCATTER || s == ENV_GEMM3M_PIPE)
       v = (!e || !e[0] || on) ? 1 : 0;  // on unless "0"
     else if (s != ENV_GEMM3M)
       v = on ? 1 : 0;
@@ -540,6 +545,7 @@ inline int plan_step(bool c128, const u64* out_labels, const u64* out_shape,
          (p.splitk == 1 && gemm3m_profitable(K, tiles)));
     p.kernel = use_3m ? TN_GEMM_C128_3M
                       : pure ? TN_GEMM_C128_PURE : TN_GEMM_C128_GLDS;
+    p.gemm_pipe = use_3m && env_switch(ENV_GEMM3M_PIPE);
   }
 
   // scatter epilogue: a non-direct out order is written by the 3M GEMM

@@ -829,13 +829,28 @@ __global__ __launch_bounds__(MF_THREADS) void k_zgemm_c128_glds_pure(
 // launcher must guarantee MF_T*K*16 and MF_K*N*16 fit in 32 bits, on top of
 // the pure-shape conditions (M % 128 == 0, N % 64 == 0, K-slices whole
 // 16-tiles). No guarded branch in the loop.
+// PIPE selects the main loop. Serial (TN_GEMM3M_PIPE=0): per 16-deep K-tile
+// 12 DMAs per wave, barrier, 96 MFMAs, barrier; a wave issues nothing while
+// its tile is in flight. Pipelined (the default): the same 48 KiB as two
+// halves of one 8-deep K-slab each, A [128][8] + B [8][64]; each half-step is
+// one plain __syncthreads(), the 6 DMAs of the other half for the next slab,
+// then the 48 MFMAs of this half. Two barriers per 16-deep tile as before,
+// the k order per accumulator is unchanged (bit-identical results), and both
+// forms build to the same budget (254 / 256 VGPRs plain / scatter, no spill,
+// 2 waves/SIMD, 49152 B). What must hold in the assembly, and is not
+// guaranteed by the source: between the two s_barrier of a tile only lgkmcnt
+// waits, vmcnt(0) in front of each barrier alone. hipcc keeps it so because
+// this body is inlined into the kernels with __restrict__ parameters (the
+// alias scopes tell the DMAs' LDS writes from the ds_reads of the other
+// half); the same loop written straight into a __global__ function drains
+// the DMAs before each half's first ds_read and runs slower than serial.
 // SCATTER selects the epilogue only; the main loop is shared. The scatter
 // epilogue stores C(row, col) at C[R(row) + Cc(col)] (ScatterMap,
 // step_plan.hpp): a wave-uniform part from the tile origin plus a tile-local
 // part from a 128-entry row table and a 64-entry column table, built in LDS
 // over As once the main loop is done. Offsets are 64-bit throughout.
 #define MF3_THREADS 256
-template <bool SCATTER>
+template <bool SCATTER, bool PIPE>
 __device__ __forceinline__ void zgemm_c128_3m_body(
     const double2* __restrict__ A, const double2* __restrict__ B,
     double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
@@ -844,9 +859,9 @@ __device__ __forceinline__ void zgemm_c128_3m_body(
   constexpr int WN = 2, FM = 4, FN = 2;
   constexpr int APIECES = TM * KT / MF3_THREADS;  // 8 glds per wave
   constexpr int BPIECES = KT * TN / MF3_THREADS;  // 4 glds per wave
-  __shared__ double2 As[TM * KT];  // [r][c ^ (r & 15)]
-  __shared__ double2 Bs[KT * TN];  // [k][j ^ ((k & 3) << 4)]
-  const int wave = threadIdx.x / 64;
+  // scalar wave index in the pipelined loop: its staging bases live in SGPRs
+  const int wave = PIPE ? __builtin_amdgcn_readfirstlane(threadIdx.x / 64)
+                        : threadIdx.x / 64;
   const int lane = threadIdx.x % 64;
   const int wm = wave / WN, wn = wave % WN;
   const unsigned tile = (unsigned)blockIdx.x % tiles;
@@ -865,57 +880,154 @@ __device__ __forceinline__ void zgemm_c128_3m_body(
     }
   const int fi = lane % 16;
   const int fk = lane / 16;
-  for (u64 k0 = kbeg; k0 < kend; k0 += KT) {
-    for (int piece = 0; piece < APIECES; ++piece) {
-      int base = (wave * APIECES + piece) * 64;
-      int i = base + lane;
-      int r = i / KT, c_sw = i % KT;
-      int c = c_sw ^ (r & 15);
-      const char* src = (const char*)(A + brow * K + k0) +
-                        (unsigned)(((unsigned)r * (unsigned)K + c) * 16u);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)&As[base], 16, 0, 0);
-    }
-    for (int piece = 0; piece < BPIECES; ++piece) {
-      int base = piece * MF3_THREADS + wave * 64;
-      int j = base + lane;
-      int k = j / TN, col_sw = j % TN;
-      int col = col_sw ^ ((k & 3) << 4);
-      const char* src = (const char*)(B + k0 * N + bcol) +
-                        (unsigned)(((unsigned)k * (unsigned)N + col) * 16u);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)&Bs[base], 16, 0, 0);
-    }
-    __syncthreads();  // carries vmcnt(0): drains the LDS-DMAs
-    for (int kq = 0; kq < KT / 4; ++kq) {
-      const int ak = kq * 4 + fk;
-      double2 a[FM], b[FN];
-      double as[FM], bs[FN];
-      for (int i = 0; i < FM; ++i) {
-        const int arow = (wm * FM + i) * 16 + fi;
-        a[i] = As[arow * KT + (ak ^ (arow & 15))];
-        as[i] = a[i].x + a[i].y;
-      }
-      for (int j = 0; j < FN; ++j) {
-        const int bcolf = (wn * FN + j) * 16 + fi;
-        b[j] = Bs[ak * TN + (bcolf ^ ((ak & 3) << 4))];
-        bs[j] = b[j].x + b[j].y;
-      }
-      for (int i = 0; i < FM; ++i)
-        for (int j = 0; j < FN; ++j) {
-          p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, p1[i][j], 0, 0, 0);
-          p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, p2[i][j], 0, 0, 0);
-          p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], p3[i][j], 0, 0, 0);
+  double2* stagebuf;  // the staging array, reused by the scatter epilogue
+  if constexpr (PIPE) {
+    // one array: a second __shared__ object can make the compiler drain the
+    // DMAs (vmcnt(0)) before every LDS read
+    __shared__ double2 lds[TM * KT + KT * TN];
+    stagebuf = lds;
+    // Two halves of one 8-deep K-slab each: A [128][c ^ ((r >> 1) & 7)],
+    // B [8][j ^ ((k & 3) << 4)], 24 KiB per half. A row is 128 B, so two
+    // rows share a 256-B bank row; the XOR by (r >> 1) & 7 puts the 8 rows of
+    // each parity of a 16-row fragment on 8 different slots whichever of the
+    // two k values the ds_read_b128 lane group carries. While the MFMAs of
+    // one half run, the DMAs of the other are in flight: the barrier that
+    // opens a half-step waits (vmcnt(0)) for DMAs issued a whole half-step
+    // earlier and frees the half about to be overwritten.
+    constexpr int KH = KT / 2;
+    constexpr int HALF = TM * KH + KH * TN;  // slots per half
+    constexpr int AP = TM * KH / MF3_THREADS;  // 4 glds per wave
+    constexpr int BP = KH * TN / MF3_THREADS;  // 2 glds per wave
+    // per-lane source offsets, bytes: piece strides and the K advance are
+    // wave-uniform and go into the scalar base. An A piece is 8 rows of 8
+    // slots; row r = (wave * AP + piece) * 8 + lane / 8 gives (r >> 1) & 7 =
+    // (lane / 16) ^ ((piece & 1) << 2), so odd pieces flip byte bit 6.
+    const unsigned offA =
+        ((unsigned)(lane / 8) * (unsigned)K + ((lane % 8) ^ (lane / 16))) *
+        16u;
+    const unsigned offB = (unsigned)(lane ^ (wave << 4)) * 16u;
+    const char* Ab = (const char*)(A + (brow + (u64)wave * (AP * 8)) * K);
+    const char* Bb = (const char*)(B + (u64)wave * N + bcol);
+    const u64 apstride = (u64)8 * K * 16, bpstride = (u64)4 * N * 16;
+    auto stage = [&](int half, u64 k) {
+      double2* Ah = lds + half * HALF;
+      double2* Bh = Ah + TM * KH;
+      const char* ak = Ab + k * 16;
+      const char* bk = Bb + k * N * 16;
+      for (int piece = 0; piece < AP; ++piece)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(
+                ak + piece * apstride + (offA ^ ((piece & 1) << 6))),
+            (__attribute__((address_space(3))) void*)&Ah[(wave * AP + piece) *
+                                                         64],
+            16, 0, 0);
+      for (int piece = 0; piece < BP; ++piece)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(
+                bk + piece * bpstride + offB),
+            (__attribute__((address_space(3))) void*)&Bh[piece * MF3_THREADS +
+                                                         wave * 64],
+            16, 0, 0);
+    };
+    auto mac = [&](int half) {
+      const double2* Ah = lds + half * HALF;
+      const double2* Bh = Ah + TM * KH;
+      for (int kq = 0; kq < KH / 4; ++kq) {
+        const int ak = kq * 4 + fk;
+        double2 a[FM], b[FN];
+        double as[FM], bs[FN];
+        for (int i = 0; i < FM; ++i) {
+          const int arow = (wm * FM + i) * 16 + fi;
+          a[i] = Ah[arow * KH + (ak ^ ((arow >> 1) & 7))];
+          as[i] = a[i].x + a[i].y;
         }
+        for (int j = 0; j < FN; ++j) {
+          const int bcolf = (wn * FN + j) * 16 + fi;
+          b[j] = Bh[ak * TN + (bcolf ^ ((ak & 3) << 4))];
+          bs[j] = b[j].x + b[j].y;
+        }
+        for (int i = 0; i < FM; ++i)
+          for (int j = 0; j < FN; ++j) {
+            p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, p1[i][j], 0, 0, 0);
+            p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, p2[i][j], 0, 0, 0);
+            p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], p3[i][j], 0, 0, 0);
+          }
+      }
+    };
+    // sched_barrier(0) pins each half's MFMAs in front of the next barrier:
+    // left alone the scheduler sinks most of them below it (their LDS reads
+    // are done by then), and that barrier's vmcnt(0) then waits for DMAs
+    // issued only a few MFMAs earlier
+    stage(0, kbeg);
+    for (u64 k0 = kbeg; k0 < kend; k0 += KT) {
+      __syncthreads();  // half 0 has landed, half 1 is free
+      stage(1, k0 + KH);
+      mac(0);
+      __builtin_amdgcn_sched_barrier(0);
+      __syncthreads();  // half 1 has landed, half 0 is free
+      // the last tile has nothing to prefetch: it stages its own first slab
+      // again (in bounds, never read) so the loop stays uniform
+      stage(0, k0 + KT < kend ? k0 + KT : k0);
+      mac(1);
+      __builtin_amdgcn_sched_barrier(0);
     }
-    __syncthreads();
+    __syncthreads();  // no DMA in flight and no reader left past this point
+  } else {
+    __shared__ double2 As[TM * KT];  // [r][c ^ (r & 15)]
+    __shared__ double2 Bs[KT * TN];  // [k][j ^ ((k & 3) << 4)]
+    stagebuf = As;
+    for (u64 k0 = kbeg; k0 < kend; k0 += KT) {
+      for (int piece = 0; piece < APIECES; ++piece) {
+        int base = (wave * APIECES + piece) * 64;
+        int i = base + lane;
+        int r = i / KT, c_sw = i % KT;
+        int c = c_sw ^ (r & 15);
+        const char* src = (const char*)(A + brow * K + k0) +
+                          (unsigned)(((unsigned)r * (unsigned)K + c) * 16u);
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)src,
+            (__attribute__((address_space(3))) void*)&As[base], 16, 0, 0);
+      }
+      for (int piece = 0; piece < BPIECES; ++piece) {
+        int base = piece * MF3_THREADS + wave * 64;
+        int j = base + lane;
+        int k = j / TN, col_sw = j % TN;
+        int col = col_sw ^ ((k & 3) << 4);
+        const char* src = (const char*)(B + k0 * N + bcol) +
+                          (unsigned)(((unsigned)k * (unsigned)N + col) * 16u);
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)src,
+            (__attribute__((address_space(3))) void*)&Bs[base], 16, 0, 0);
+      }
+      __syncthreads();  // carries vmcnt(0): drains the LDS-DMAs
+      for (int kq = 0; kq < KT / 4; ++kq) {
+        const int ak = kq * 4 + fk;
+        double2 a[FM], b[FN];
+        double as[FM], bs[FN];
+        for (int i = 0; i < FM; ++i) {
+          const int arow = (wm * FM + i) * 16 + fi;
+          a[i] = As[arow * KT + (ak ^ (arow & 15))];
+          as[i] = a[i].x + a[i].y;
+        }
+        for (int j = 0; j < FN; ++j) {
+          const int bcolf = (wn * FN + j) * 16 + fi;
+          b[j] = Bs[ak * TN + (bcolf ^ ((ak & 3) << 4))];
+          bs[j] = b[j].x + b[j].y;
+        }
+        for (int i = 0; i < FM; ++i)
+          for (int j = 0; j < FN; ++j) {
+            p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, p1[i][j], 0, 0, 0);
+            p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, p2[i][j], 0, 0, 0);
+            p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], p3[i][j], 0, 0, 0);
+          }
+      }
+      __syncthreads();
+    }
   }
   const int ccol = lane % 16;
   if constexpr (SCATTER) {
-    // the loop's closing barrier has retired every read of As
-    u64* rowtab = (u64*)As;
+    // the loop's closing barrier has retired every read of the staging array
+    u64* rowtab = (u64*)stagebuf;
     u64* coltab = rowtab + TM;
     const int t = threadIdx.x;
     if (t < TM + TN) {
@@ -961,8 +1073,17 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m(
     const double2* __restrict__ A, const double2* __restrict__ B,
     double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
     unsigned tiles, u64 kchunk) {
-  zgemm_c128_3m_body<false>(A, B, C, M, N, K, col_tiles, tiles, kchunk,
-                            nullptr);
+  zgemm_c128_3m_body<false, false>(A, B, C, M, N, K, col_tiles, tiles, kchunk,
+                                   nullptr);
+}
+
+__global__ __launch_bounds__(MF3_THREADS)
+__attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m_pipe(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
+    unsigned tiles, u64 kchunk) {
+  zgemm_c128_3m_body<false, true>(A, B, C, M, N, K, col_tiles, tiles, kchunk,
+                                  nullptr);
 }
 
 // Launched unsplit only (tiles == grid): the map covers one M x N output.
@@ -971,7 +1092,18 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void k_zgemm_c128_glds_3m_scatter(
     const double2* __restrict__ A, const double2* __restrict__ B,
     double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
     unsigned tiles, u64 kchunk, ScatterMap sm) {
-  zgemm_c128_3m_body<true>(A, B, C, M, N, K, col_tiles, tiles, kchunk, &sm);
+  zgemm_c128_3m_body<true, false>(A, B, C, M, N, K, col_tiles, tiles, kchunk,
+                                  &sm);
+}
+
+__global__ __launch_bounds__(MF3_THREADS)
+__attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_zgemm_c128_glds_3m_scatter_pipe(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles,
+    unsigned tiles, u64 kchunk, ScatterMap sm) {
+  zgemm_c128_3m_body<true, true>(A, B, C, M, N, K, col_tiles, tiles, kchunk,
+                                 &sm);
 }
 
 
@@ -1762,10 +1894,14 @@ static int ttgt_serial(const Step<CT>& s, CT* Cg, WsBlock<CT>& packA,
       k_zgemm_c128_glds_gather<<<grid, MF_THREADS, 0, s.stream>>>(
           s.Adata, s.Bdata, gemm_out, M, N, K, ct, nt, kchunk, p.gmA, p.gmB);
     else if (p.kernel == TN_GEMM_C128_3M && p.scatter_out)
-      k_zgemm_c128_glds_3m_scatter<<<grid, MF3_THREADS, 0, s.stream>>>(
+      (p.gemm_pipe ? k_zgemm_c128_glds_3m_scatter_pipe
+                   : k_zgemm_c128_glds_3m_scatter)<<<grid, MF3_THREADS, 0,
+                                                     s.stream>>>(
           Ag, Bg, gemm_out, M, N, K, ct, nt, kchunk, p.smap);
     else if (p.kernel == TN_GEMM_C128_3M)
-      k_zgemm_c128_glds_3m<<<grid, MF3_THREADS, 0, s.stream>>>(
+      (p.gemm_pipe ? k_zgemm_c128_glds_3m_pipe
+                   : k_zgemm_c128_glds_3m)<<<grid, MF3_THREADS, 0,
+                                             s.stream>>>(
           Ag, Bg, gemm_out, M, N, K, ct, nt, kchunk);
     else if (p.kernel == TN_GEMM_C128_PURE)
       k_zgemm_c128_glds_pure<<<grid, MF_THREADS, 0, s.stream>>>(

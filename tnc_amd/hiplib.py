@@ -132,6 +132,7 @@ class StepPlan(ctypes.Structure):
         ("ws_tmp_c", ctypes.c_uint64), ("ws_slices", ctypes.c_uint64),
         ("ws_split", ctypes.c_uint64), ("ws_dot", ctypes.c_uint64),
         ("scatter_out", ctypes.c_int32),
+        ("gemm_pipe", ctypes.c_int32),
     ]
 
 
