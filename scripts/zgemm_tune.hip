@@ -534,6 +534,240 @@ static void launch_3mp(const double2* A, const double2* B, double2* C, u64 M,
                      C, M, N, K, (unsigned)ct);
 }
 
+// Pipelined 3M on the 128x64 tile with the instruction order of a half-step
+// written down: every group of instructions sits between two
+// sched_barrier(0), so the source order below is the order in the assembly.
+// Same halves, swizzles, staging addresses and k order per accumulator as
+// zg_glds_3m_pipe_body, hence bit-identical to it and to 3M-A. S adds up:
+//  1  after the barrier the fragment reads of the first k-quad come before
+//     the six DMAs (their issue lies under the LDS latency);
+//  2  the DMAs go among the MFMAs of the first k-quad instead, one piece per
+//     two MFMAs, the last one after the 16th MFMA of the half-step;
+//  3  a half-step is 8 row blocks of 6 MFMAs (k-quad q, fragment row i); the
+//     A fragment of block t+1 is read at the head of block t, the B
+//     fragments of the second quad in block 2 (a[0], a[1] are dead by then),
+//     each operand sum is formed at the head of the next block, in front of
+//     that block's reads (hipcc turns every lgkmcnt into lgkmcnt(0) while an
+//     LDS-DMA is pending, so the wait is placed where nothing younger is
+//     outstanding); never more fragment registers live than the 36 of one
+//     quad;
+//  4  the half-step's barrier moves in front of its last row block: behind
+//     it come the first reads of the other half, then the 6 tail MFMAs
+//     (registers only), so no wave meets the barrier's far side with an
+//     empty pipe. The lgkmcnt(0) in front of the barrier retires every read
+//     of the half it frees; the DMAs its vmcnt(0) drains are 26 MFMAs old.
+// DSHIFT moves the DMA pieces of S >= 2 back by whole row blocks (0: row
+// blocks 0-2 of the half-step, 1: row blocks 1-3).
+#define ZG_FENCE() __builtin_amdgcn_sched_barrier(0)
+template <int S, int DSHIFT>
+__device__ __forceinline__ void zg_glds_3m_sched_body(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles) {
+  constexpr int WN = 2, FM = 4, FN = 2, NT = 256;
+  constexpr int TM = 128, TN = 64, KT = 16, KH = 8;
+  constexpr int HALF = TM * KH + KH * TN;
+  constexpr int AP = TM * KH / NT, BP = KH * TN / NT;
+  __shared__ double2 lds[2 * HALF];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+  const int lane = threadIdx.x % 64;
+  const int wm = wave / WN, wn = wave % WN;
+  const unsigned tile = blockIdx.x;
+  const u64 brow = (u64)(tile / col_tiles) * TM;
+  const u64 bcol = (u64)(tile % col_tiles) * TN;
+  v4d p1[FM][FN], p2[FM][FN], p3[FM][FN];
+  for (int i = 0; i < FM; ++i)
+    for (int j = 0; j < FN; ++j) {
+      p1[i][j] = v4d{0, 0, 0, 0};
+      p2[i][j] = v4d{0, 0, 0, 0};
+      p3[i][j] = v4d{0, 0, 0, 0};
+    }
+  const int fi = lane % 16;
+  const int fk = lane / 16;
+  const unsigned offA =
+      ((unsigned)(lane / 8) * (unsigned)K + ((lane % 8) ^ (lane / 16))) * 16u;
+  const unsigned offB = (unsigned)(lane ^ (wave << 4)) * 16u;
+  const char* Ab = (const char*)(A + (brow + (u64)wave * (AP * 8)) * K);
+  const char* Bb = (const char*)(B + (u64)wave * N + bcol);
+  const u64 apstride = (u64)8 * K * 16, bpstride = (u64)4 * N * 16;
+  // DMA piece p of slab k into `half`: 0..3 are A's, 4..5 are B's
+  auto dma = [&](int half, u64 k, int p) {
+    double2* Ah = lds + half * HALF;
+    double2* Bh = Ah + TM * KH;
+    if (p < AP)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)(
+              Ab + k * 16 + p * apstride + (offA ^ ((p & 1) << 6))),
+          (__attribute__((address_space(3))) void*)&Ah[(wave * AP + p) * 64],
+          16, 0, 0);
+    else
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)(
+              Bb + k * N * 16 + (p - AP) * bpstride + offB),
+          (__attribute__((address_space(3))) void*)&Bh[(p - AP) * NT +
+                                                       wave * 64],
+          16, 0, 0);
+  };
+  auto rdA = [&](int half, int q, int i) {
+    const int ak = q * 4 + fk;
+    const int arow = (wm * FM + i) * 16 + fi;
+    return lds[half * HALF + arow * KH + (ak ^ ((arow >> 1) & 7))];
+  };
+  auto rdB = [&](int half, int q, int j) {
+    const int ak = q * 4 + fk;
+    const int bcolf = (wn * FN + j) * 16 + fi;
+    return lds[half * HALF + TM * KH + ak * TN + (bcolf ^ ((ak & 3) << 4))];
+  };
+  auto mfma3 = [&](int i, int j, double2 a, double as, double2 b, double bs) {
+    p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, p1[i][j], 0, 0, 0);
+    p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.y, p2[i][j], 0, 0, 0);
+    p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as, bs, p3[i][j], 0, 0, 0);
+  };
+  // one row block: 6 MFMAs, with DMA pieces d0, d0 + 1 of slab kn behind the
+  // second and the fourth when d0 >= 0
+  auto block = [&](int i, double2 a, double as, const double2* b,
+                   const double* bs, int half, u64 kn, int d0) {
+    p1[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b[0].x, p1[i][0], 0, 0, 0);
+    p2[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b[0].y, p2[i][0], 0, 0, 0);
+    ZG_FENCE();
+    if (d0 >= 0) dma(half ^ 1, kn, d0);
+    ZG_FENCE();
+    p3[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(as, bs[0], p3[i][0], 0, 0, 0);
+    p1[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b[1].x, p1[i][1], 0, 0, 0);
+    ZG_FENCE();
+    if (d0 >= 0) dma(half ^ 1, kn, d0 + 1);
+    ZG_FENCE();
+    p2[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b[1].y, p2[i][1], 0, 0, 0);
+    p3[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(as, bs[1], p3[i][1], 0, 0, 0);
+    ZG_FENCE();
+  };
+  if constexpr (S <= 2) {
+    auto halfstep = [&](int half, u64 kn) {
+      __syncthreads();
+      ZG_FENCE();
+      double2 a[FM], b[FN];
+      double as[FM], bs[FN];
+      for (int i = 0; i < FM; ++i) a[i] = rdA(half, 0, i);
+      for (int j = 0; j < FN; ++j) b[j] = rdB(half, 0, j);
+      ZG_FENCE();
+      if (S == 1) {
+        for (int p = 0; p < AP + BP; ++p) dma(half ^ 1, kn, p);
+        ZG_FENCE();
+      }
+      for (int i = 0; i < FM; ++i) as[i] = a[i].x + a[i].y;
+      for (int j = 0; j < FN; ++j) bs[j] = b[j].x + b[j].y;
+      ZG_FENCE();
+      for (int i = 0; i < FM; ++i) {
+        const int d0 = 2 * (i - DSHIFT);
+        block(i, a[i], as[i], b, bs, half, kn,
+              S == 2 && d0 >= 0 && d0 < AP + BP ? d0 : -1);
+      }
+      // second quad: the compiler's own order, as in zg_glds_3m_pipe_body
+      for (int i = 0; i < FM; ++i) {
+        a[i] = rdA(half, 1, i);
+        as[i] = a[i].x + a[i].y;
+      }
+      for (int j = 0; j < FN; ++j) {
+        b[j] = rdB(half, 1, j);
+        bs[j] = b[j].x + b[j].y;
+      }
+      for (int i = 0; i < FM; ++i)
+        for (int j = 0; j < FN; ++j) mfma3(i, j, a[i], as[i], b[j], bs[j]);
+      ZG_FENCE();
+    };
+    for (int p = 0; p < AP + BP; ++p) dma(0, 0, p);
+    for (u64 k0 = 0; k0 < K; k0 += KT) {
+      halfstep(0, k0 + KH);
+      halfstep(1, k0 + KT < K ? k0 + KT : k0);  // last tile: restage
+    }
+  } else {
+    constexpr bool TAIL = S >= 4;
+    // fragments in flight across row blocks: B of the quad in use (cb, cbs),
+    // B of the next quad (nb), A of the block in use (ca, cas) and of the
+    // next block (na). With TAIL the first three reads of a half-step are
+    // issued in the previous one and carried over.
+    double2 cb[FN], nb[FN], ca, na;
+    double cbs[FN], cas;
+    auto head = [&](int half) {  // B of quad 0 and A of block 0
+      for (int j = 0; j < FN; ++j) nb[j] = rdB(half, 0, j);
+      na = rdA(half, 0, 0);
+      ZG_FENCE();
+    };
+    auto halfstep = [&](int half, u64 kn) {
+      if (!TAIL) {
+        __syncthreads();
+        ZG_FENCE();
+        head(half);
+      }
+      for (int t = 0; t < 8; ++t) {
+        const int i = t % 4;
+        // what the previous block read has had its 6 MFMAs: the wait in
+        // front of these sums has no younger read to wait for
+        ca = na;
+        cas = ca.x + ca.y;
+        if (i == 0)
+          for (int j = 0; j < FN; ++j) {
+            cb[j] = nb[j];
+            cbs[j] = nb[j].x + nb[j].y;
+          }
+        ZG_FENCE();
+        if (TAIL && t == 7) {
+          // retires every read of this half and the DMAs of blocks 0-2
+          __syncthreads();
+          ZG_FENCE();
+        }
+        // reads for the next block
+        if (t < 7) na = rdA(half, (t + 1) / 4, (t + 1) % 4);
+        if (t == 2)
+          for (int j = 0; j < FN; ++j) nb[j] = rdB(half, 1, j);
+        if (TAIL && t == 7) head(half ^ 1);
+        ZG_FENCE();
+        const int d0 = 2 * (t - DSHIFT);
+        block(i, ca, cas, cb, cbs, half, kn,
+              d0 >= 0 && d0 < AP + BP ? d0 : -1);
+      }
+    };
+    for (int p = 0; p < AP + BP; ++p) dma(0, 0, p);
+    if (TAIL) {
+      __syncthreads();
+      ZG_FENCE();
+      head(0);
+    }
+    for (u64 k0 = 0; k0 < K; k0 += KT) {
+      halfstep(0, k0 + KH);
+      halfstep(1, k0 + KT < K ? k0 + KT : k0);  // last tile: restage
+    }
+  }
+  __syncthreads();  // no DMA in flight, no reader left
+  const int ccol = lane % 16;
+  for (int i = 0; i < FM; ++i)
+    for (int j = 0; j < FN; ++j)
+      for (int r = 0; r < 4; ++r) {
+        u64 row = brow + (wm * FM + i) * 16 + (lane / 16) + 4 * r;
+        u64 col = bcol + (wn * FN + j) * 16 + ccol;
+        C[row * N + col] = make_double2(
+            p1[i][j][r] - p2[i][j][r],
+            (p3[i][j][r] - p1[i][j][r]) - p2[i][j][r]);
+      }
+}
+
+template <int S, int DSHIFT>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(2, 2))) void zg_glds_3m_sched(
+    const double2* __restrict__ A, const double2* __restrict__ B,
+    double2* __restrict__ C, u64 M, u64 N, u64 K, unsigned col_tiles) {
+  zg_glds_3m_sched_body<S, DSHIFT>(A, B, C, M, N, K, col_tiles);
+}
+
+template <int S, int DSHIFT>
+static void launch_3ms(const double2* A, const double2* B, double2* C, u64 M,
+                       u64 N, u64 K) {
+  if (M % 128 || N % 64 || K % 16) return;
+  if ((u64)128 * K * 16 > 0xffffffffull || 16 * N * 16 > 0xffffffffull) return;
+  u64 rt = M / 128, ct = N / 64;
+  hipLaunchKernelGGL((zg_glds_3m_sched<S, DSHIFT>), dim3((unsigned)(rt * ct)),
+                     dim3(256), 0, 0, A, B, C, M, N, K, (unsigned)ct);
+}
+
 struct Variant {
   const char* name;
   void (*launch)(const double2*, const double2*, double2*, u64, u64, u64);
@@ -604,6 +838,11 @@ int main(int argc, char** argv) {
       {"3M-A pipe 128x64 e2", launch_3mp<2, 2, 4, 2, 2, true>},
       {"3M-B pipe 64x64 e3", launch_3mp<2, 2, 2, 2, 3, true>},
       {"3M-A pipe, unpinned", launch_3mp<2, 2, 4, 2, 2, false>},
+      {"3M-A sched 1", launch_3ms<1, 0>},
+      {"3M-A sched 1+2", launch_3ms<2, 0>},
+      {"3M-A sched 1+2+3", launch_3ms<3, 0>},
+      {"3M-A sched 1+2+3+4", launch_3ms<4, 0>},
+      {"3M-A sched 1-4, DMA +1", launch_3ms<4, 1>},
   };
   if (all) {
     variants.push_back({"w8 k16 planar", launch_zg<8, 16, 0>});

@@ -832,24 +832,46 @@ __global__ __launch_bounds__(MF_THREADS) void k_zgemm_c128_glds_pure(
 // PIPE selects the main loop. Serial (TN_GEMM3M_PIPE=0): per 16-deep K-tile
 // 12 DMAs per wave, barrier, 96 MFMAs, barrier; a wave issues nothing while
 // its tile is in flight. Pipelined (the default): the same 48 KiB as two
-// halves of one 8-deep K-slab each, A [128][8] + B [8][64]; each half-step is
-// one plain __syncthreads(), the 6 DMAs of the other half for the next slab,
-// then the 48 MFMAs of this half. Two barriers per 16-deep tile as before,
-// the k order per accumulator is unchanged (bit-identical results), and both
-// forms build to the same budget (254 / 256 VGPRs plain / scatter, no spill,
-// 2 waves/SIMD, 49152 B). What must hold in the assembly, and is not
-// guaranteed by the source: between the two s_barrier of a tile only lgkmcnt
-// waits, vmcnt(0) in front of each barrier alone. hipcc keeps it so because
-// this body is inlined into the kernels with __restrict__ parameters (the
-// alias scopes tell the DMAs' LDS writes from the ds_reads of the other
-// half); the same loop written straight into a __global__ function drains
-// the DMAs before each half's first ds_read and runs slower than serial.
+// halves of one 8-deep K-slab each, A [128][8] + B [8][64]; the DMAs of one
+// half fly under the MFMAs of the other. Two barriers per 16-deep tile as
+// before, the k order per accumulator is unchanged (bit-identical results),
+// and both forms build to the same budget (254 / 256 VGPRs plain / scatter,
+// no spill, 2 waves/SIMD, 49152 B).
+// The pipelined half-step, in source order and, through sched_barrier(0)
+// between the groups, in the assembly: barrier; the 6 fragment reads of the
+// first k-quad; their 6 operand sums; the first quad's 24 MFMAs with the 6
+// DMA pieces of the next slab behind MFMAs 2, 4, 8, 10, 14 and 16; then the
+// second quad (6 reads, 6 sums, 24 MFMAs) in the compiler's order, fenced in
+// front of the next barrier. The reads come before the DMAs so that the
+// DMAs' issue does not stand in front of the LDS latency, and the DMAs go
+// one by one under the MFMAs instead of six in a row in front of them; the
+// last piece is 32 MFMAs old when the next barrier's vmcnt(0) asks for it.
+// A finer schedule (fragments of the next row block read under each row
+// block's 6 MFMAs, the barrier moved in front of the last row block) keeps
+// each wave's own pipe fed without a gap and measured slower than this one:
+// what covers a wave's two read gaps per half-step is the other block's wave
+// on the same SIMD, and every instruction put between a wave's MFMAs costs
+// it more than the gap does (profiles/r07_gemm3m_sched.md).
+// The speed rests on these properties of the assembly (check them after a
+// compiler change; kernel-resource-usage remarks and the loop body):
+// exactly two s_barrier per loop trip, each with s_waitcnt vmcnt(0) in front
+// and no other vmcnt wait; 6 global_load_lds and 48 MFMAs per half-step in
+// the order above; <= 256 VGPRs, no scratch. The source pins the barriers,
+// the first quad's reads, the DMAs and the first quad's MFMAs. It does not
+// guarantee (1) that no vmcnt appears in front of a ds_read: hipcc keeps it
+// out because this body is inlined into the kernels with __restrict__
+// parameters (the alias scopes tell the DMAs' LDS writes from the ds_reads
+// of the other half), and the same loop written straight into a __global__
+// function drains the DMAs before the reads and runs slower than serial;
+// (2) the order inside the second quad; (3) counted lgkmcnt(N) waits: hipcc
+// turns every lgkmcnt into lgkmcnt(0) while an LDS-DMA is pending.
 // SCATTER selects the epilogue only; the main loop is shared. The scatter
 // epilogue stores C(row, col) at C[R(row) + Cc(col)] (ScatterMap,
 // step_plan.hpp): a wave-uniform part from the tile origin plus a tile-local
 // part from a 128-entry row table and a 64-entry column table, built in LDS
 // over As once the main loop is done. Offsets are 64-bit throughout.
 #define MF3_THREADS 256
+#define MF3_FENCE() __builtin_amdgcn_sched_barrier(0)
 template <bool SCATTER, bool PIPE>
 __device__ __forceinline__ void zgemm_c128_3m_body(
     const double2* __restrict__ A, const double2* __restrict__ B,
@@ -892,8 +914,9 @@ __device__ __forceinline__ void zgemm_c128_3m_body(
     // each parity of a 16-row fragment on 8 different slots whichever of the
     // two k values the ds_read_b128 lane group carries. While the MFMAs of
     // one half run, the DMAs of the other are in flight: the barrier that
-    // opens a half-step waits (vmcnt(0)) for DMAs issued a whole half-step
-    // earlier and frees the half about to be overwritten.
+    // opens a half-step waits (vmcnt(0)) for the DMAs issued under the
+    // first k-quad of the half-step before and frees the half about to be
+    // overwritten.
     constexpr int KH = KT / 2;
     constexpr int HALF = TM * KH + KH * TN;  // slots per half
     constexpr int AP = TM * KH / MF3_THREADS;  // 4 glds per wave
@@ -909,67 +932,95 @@ __device__ __forceinline__ void zgemm_c128_3m_body(
     const char* Ab = (const char*)(A + (brow + (u64)wave * (AP * 8)) * K);
     const char* Bb = (const char*)(B + (u64)wave * N + bcol);
     const u64 apstride = (u64)8 * K * 16, bpstride = (u64)4 * N * 16;
-    auto stage = [&](int half, u64 k) {
+    // DMA piece p of slab k into `half`: 0..3 are A's, 4..5 are B's
+    auto dma = [&](int half, u64 k, int p) {
       double2* Ah = lds + half * HALF;
       double2* Bh = Ah + TM * KH;
-      const char* ak = Ab + k * 16;
-      const char* bk = Bb + k * N * 16;
-      for (int piece = 0; piece < AP; ++piece)
+      if (p < AP)
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) void*)(
-                ak + piece * apstride + (offA ^ ((piece & 1) << 6))),
-            (__attribute__((address_space(3))) void*)&Ah[(wave * AP + piece) *
-                                                         64],
+                Ab + k * 16 + p * apstride + (offA ^ ((p & 1) << 6))),
+            (__attribute__((address_space(3))) void*)&Ah[(wave * AP + p) * 64],
             16, 0, 0);
-      for (int piece = 0; piece < BP; ++piece)
+      else
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) void*)(
-                bk + piece * bpstride + offB),
-            (__attribute__((address_space(3))) void*)&Bh[piece * MF3_THREADS +
+                Bb + k * N * 16 + (p - AP) * bpstride + offB),
+            (__attribute__((address_space(3))) void*)&Bh[(p - AP) *
+                                                             MF3_THREADS +
                                                          wave * 64],
             16, 0, 0);
     };
-    auto mac = [&](int half) {
-      const double2* Ah = lds + half * HALF;
-      const double2* Bh = Ah + TM * KH;
-      for (int kq = 0; kq < KH / 4; ++kq) {
-        const int ak = kq * 4 + fk;
-        double2 a[FM], b[FN];
-        double as[FM], bs[FN];
-        for (int i = 0; i < FM; ++i) {
-          const int arow = (wm * FM + i) * 16 + fi;
-          a[i] = Ah[arow * KH + (ak ^ ((arow >> 1) & 7))];
-          as[i] = a[i].x + a[i].y;
-        }
-        for (int j = 0; j < FN; ++j) {
-          const int bcolf = (wn * FN + j) * 16 + fi;
-          b[j] = Bh[ak * TN + (bcolf ^ ((ak & 3) << 4))];
-          bs[j] = b[j].x + b[j].y;
-        }
-        for (int i = 0; i < FM; ++i)
-          for (int j = 0; j < FN; ++j) {
-            p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, p1[i][j], 0, 0, 0);
-            p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, p2[i][j], 0, 0, 0);
-            p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], p3[i][j], 0, 0, 0);
-          }
-      }
+    auto rdA = [&](int half, int q, int i) {
+      const int ak = q * 4 + fk;
+      const int arow = (wm * FM + i) * 16 + fi;
+      return lds[half * HALF + arow * KH + (ak ^ ((arow >> 1) & 7))];
     };
-    // sched_barrier(0) pins each half's MFMAs in front of the next barrier:
-    // left alone the scheduler sinks most of them below it (their LDS reads
-    // are done by then), and that barrier's vmcnt(0) then waits for DMAs
-    // issued only a few MFMAs earlier
-    stage(0, kbeg);
+    auto rdB = [&](int half, int q, int j) {
+      const int ak = q * 4 + fk;
+      const int bcolf = (wn * FN + j) * 16 + fi;
+      return lds[half * HALF + TM * KH + ak * TN + (bcolf ^ ((ak & 3) << 4))];
+    };
+    // One half-step. Every group of instructions up to the second k-quad
+    // sits between two sched_barrier(0): the order below is the order in
+    // the assembly.
+    auto halfstep = [&](int half, u64 kn) {
+      __syncthreads();  // this half has landed, the other one is free
+      MF3_FENCE();
+      double2 a[FM], b[FN];
+      double as[FM], bs[FN];
+      // the first k-quad's fragments before any DMA: the DMAs' issue does
+      // not stand in front of the LDS latency
+      for (int i = 0; i < FM; ++i) a[i] = rdA(half, 0, i);
+      for (int j = 0; j < FN; ++j) b[j] = rdB(half, 0, j);
+      MF3_FENCE();
+      for (int i = 0; i < FM; ++i) as[i] = a[i].x + a[i].y;
+      for (int j = 0; j < FN; ++j) bs[j] = b[j].x + b[j].y;
+      MF3_FENCE();
+      // first k-quad: 4 row blocks of 6 MFMAs; blocks 0-2 carry the 6 DMA
+      // pieces of the next slab, one behind the 2nd and one behind the 4th
+      // MFMA, so the last piece is 32 MFMAs old at the next vmcnt(0)
+      for (int i = 0; i < FM; ++i) {
+        const int d0 = i < 3 ? 2 * i : -1;
+        p1[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[0].x, p1[i][0], 0, 0, 0);
+        p2[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[0].y, p2[i][0], 0, 0, 0);
+        MF3_FENCE();
+        if (d0 >= 0) dma(half ^ 1, kn, d0);
+        MF3_FENCE();
+        p3[i][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[0], p3[i][0], 0, 0, 0);
+        p1[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[1].x, p1[i][1], 0, 0, 0);
+        MF3_FENCE();
+        if (d0 >= 0) dma(half ^ 1, kn, d0 + 1);
+        MF3_FENCE();
+        p2[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[1].y, p2[i][1], 0, 0, 0);
+        p3[i][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[1], p3[i][1], 0, 0, 0);
+        MF3_FENCE();
+      }
+      // second k-quad: reads, sums, 24 MFMAs, in the compiler's order; the
+      // fences on either side keep all of it behind the first quad and in
+      // front of the next barrier
+      for (int i = 0; i < FM; ++i) {
+        a[i] = rdA(half, 1, i);
+        as[i] = a[i].x + a[i].y;
+      }
+      for (int j = 0; j < FN; ++j) {
+        b[j] = rdB(half, 1, j);
+        bs[j] = b[j].x + b[j].y;
+      }
+      for (int i = 0; i < FM; ++i)
+        for (int j = 0; j < FN; ++j) {
+          p1[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, b[j].x, p1[i][j], 0, 0, 0);
+          p2[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, b[j].y, p2[i][j], 0, 0, 0);
+          p3[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[i], bs[j], p3[i][j], 0, 0, 0);
+        }
+      MF3_FENCE();
+    };
+    for (int p = 0; p < AP + BP; ++p) dma(0, kbeg, p);
     for (u64 k0 = kbeg; k0 < kend; k0 += KT) {
-      __syncthreads();  // half 0 has landed, half 1 is free
-      stage(1, k0 + KH);
-      mac(0);
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();  // half 1 has landed, half 0 is free
+      halfstep(0, k0 + KH);
       // the last tile has nothing to prefetch: it stages its own first slab
       // again (in bounds, never read) so the loop stays uniform
-      stage(0, k0 + KT < kend ? k0 + KT : k0);
-      mac(1);
-      __builtin_amdgcn_sched_barrier(0);
+      halfstep(1, k0 + KT < kend ? k0 + KT : k0);
     }
     __syncthreads();  // no DMA in flight and no reader left past this point
   } else {
