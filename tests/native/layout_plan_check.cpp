@@ -1,5 +1,6 @@
 // Stand-alone host check of the scatter-epilogue gate (plan_step) and the
-// layout pre-pass (plan_layouts). Needs only a host compiler, e.g.
+// walk plan (plan_layouts: stored orders, look-ahead packs, inline pack
+// bytes). Needs only a host compiler, e.g.
 //   g++ -std=c++17 -O1 -g -Wall -fsanitize=address,undefined
 //       -fno-sanitize-recover=undefined tests/native/layout_plan_check.cpp
 // Exit 0 and "layout_plan_check OK" on success. With TN_EPI_SCATTER=0 in the
@@ -200,6 +201,50 @@ int main() {
     const u64 bad[] = {0, 1, 1, 2};
     plan_layouts(true, leaves, bad, 2, &lp);
     CHECK(!lp.valid);
+  }
+
+  // walk plan of a four-leaf network whose three steps are all TTGT:
+  //   0 = M+K, 1 = K+N, 2 = X+K1, 3 = K2+Y      path (0,1) (0,2) (3,0)
+  // 2048x1024x32, then 2048x64x1024 against leaf 2, then 128x64x2048 with
+  // leaf 3 as A. Step 1 can pack only its B early (step 0 makes its A),
+  // step 2 only its A (step 1 makes its B).
+  {
+    const Legs X = legs(400, 6), Y = legs(500, 7);
+    const Legs k1 = cat({sub(M, 5, 11), sub(N, 6, 10)});
+    const Legs k2 = cat({X, sub(N, 0, 5)});
+    std::vector<LayoutTensor> leaves = {
+        tensor(cat({M, K})), tensor(cat({K, N})), tensor(cat({X, k1})),
+        tensor(cat({k2, Y}))};
+    const u64 pairs[] = {0, 1, 0, 2, 3, 0};
+    LayoutPlan lp;
+    plan_layouts(true, leaves, pairs, 3, &lp);
+    CHECK(lp.valid && lp.out.size() == 3 && lp.early.size() == 3);
+    const Legs rows1 = cat({sub(M, 0, 5), sub(N, 0, 6)});
+    CHECK(lp.out[0].labels == (on ? cat({rows1, k1}) : cat({M, N})));
+    CHECK(lp.out[1].labels == cat({rows1, X}));
+    CHECK(lp.out[2].labels == cat({Y, sub(M, 0, 5), sub(N, 5, 6)}));
+    CHECK(lp.scatter_out == std::vector<int32_t>({on ? 1 : 0, 0, 0}));
+    // look-ahead packs: the same with the scatter epilogue on and off
+    const EarlyPack &e0 = lp.early[0], &e1 = lp.early[1], &e2 = lp.early[2];
+    CHECK(!e0.a && !e0.b);
+    CHECK(!e1.a && e1.b && e1.a_elems == 0 && e1.b_elems == (1ull << 16));
+    std::vector<int> k1_then_x, y_then_k2;  // leaf 2 as [K1][X], 3 as [Y][K2]
+    for (int x = 0; x < 16; ++x) k1_then_x.push_back((x + 6) % 16);
+    for (int x = 0; x < 18; ++x) y_then_k2.push_back((x + 11) % 18);
+    CHECK(e1.a_axes.empty() && e1.b_axes == k1_then_x);
+    CHECK(e2.a && !e2.b && e2.a_elems == (1ull << 18) && e2.b_elems == 0);
+    CHECK(e2.a_axes == y_then_k2 && e2.b_axes.empty());
+    // inline: step 1's A only when step 0 stored the plain order, step 2's B
+    CHECK(lp.inline_pack_bytes ==
+          std::vector<u64>({0, on ? 0 : (1ull << 21) * 16, (1ull << 17) * 16}));
+    // no plan: a dead operand, and a leaf of rank 41
+    const u64 bad[] = {0, 1, 1, 2, 3, 0};
+    plan_layouts(true, leaves, bad, 3, &lp);
+    CHECK(!lp.valid && lp.err == "invalid contraction path step");
+    CHECK(lp.out.empty() && lp.early.empty());
+    leaves[3] = tensor(legs(600, 41));
+    plan_layouts(true, leaves, pairs, 3, &lp);
+    CHECK(!lp.valid && lp.err == "tensor rank exceeds 40");
   }
   printf("layout_plan_check OK (scatter %s)\n", on ? "on" : "off");
   return 0;

@@ -32,16 +32,26 @@ CHAIN_BYTES = {436: 2 ** 31 * 16, 437: 2 ** 29 * 16, 438: 2 ** 26 * 16,
                439: 2 ** 28 * 16}
 
 LAYOUT_CHILD = r"""
-import json
+import json, sys
 from tnc_amd import hiplib
 from tnc_amd.contraction_path import ContractionPath, flatten_network
 from tnc_amd.fixtures import load_fixture
-tn, replace_toplevel, _ = load_fixture("rqc36")
+fixture, dtype = sys.argv[1:3] if len(sys.argv) > 2 else ("rqc36", "c128")
+tn, replace_toplevel, _ = load_fixture(fixture)
 leaves, steps, _ = flatten_network(tn, ContractionPath.simple(replace_toplevel))
 scatter, inline = hiplib.plan_layouts(
-    [(t.legs, t.bond_dims) for t in leaves], steps)
+    [(t.legs, t.bond_dims) for t in leaves], steps, dtype=dtype)
 print("LAYOUT " + json.dumps({"scatter": scatter, "inline": inline}))
 """
+
+# sum(inline_pack_bytes) of the frozen paths, as planned before the look-ahead
+# rule moved into the pre-pass: (fixture, dtype, TN_EPI_SCATTER) -> bytes
+INLINE_PINS = [
+    ("rqc36", "c128", None, 1_480_720_384),
+    ("rqc36", "c128", "0", 50_604_408_832),
+    ("syc49", "c64", None, 103_079_215_104),
+    ("rqc24", "c128", None, 0),
+]
 
 PLAN_CHILD = r"""
 import json, sys
@@ -98,6 +108,13 @@ def test_inline_packs_fall_below_five_percent(layout_on, layout_off):
     on, off = sum(layout_on["inline"]), sum(layout_off["inline"])
     print("inline pack bytes: on", on, "off", off)
     assert on < 0.05 * off
+
+
+@pytest.mark.parametrize("fixture,dtype,scatter_env,total", INLINE_PINS)
+def test_inline_pack_totals_are_pinned(fixture, dtype, scatter_env, total):
+    env = {} if scatter_env is None else {"TN_EPI_SCATTER": scatter_env}
+    got = run_child(LAYOUT_CHILD, "LAYOUT", env, fixture, dtype)
+    assert sum(got["inline"]) == total
 
 
 # ---- plan_step route table: the scatter gate ------------------------------

@@ -4,9 +4,10 @@
 // a StepPlan: route (dot / gather / TTGT), which operands get packed, the
 // pack-pipeline windows, split-K, the GEMM kernel and the workspace the step
 // will ask for. No HIP call, no HIP header: it builds with a plain host
-// compiler and runs without a GPU. The executor (einsum_dev_impl), the
-// prepack look-ahead (plan_prepack) and the Python arena model (through
-// tn_plan_step) all read this plan; none re-derives it. Only what depends on
+// compiler and runs without a GPU. The executor (einsum_dev_impl), the walk
+// plan of a whole path (plan_layouts, below: stored orders and look-ahead
+// packs) and the Python arena model (through tn_plan_step) all read this
+// plan; none re-derives it. Only what depends on
 // an allocation failing at run time stays in the executor: split-K falling
 // back to 1, the pipeline to the serial pack, out-of-memory to the gather
 // route.
@@ -572,11 +573,14 @@ inline int plan_step(bool c128, const u64* out_labels, const u64* out_shape,
   return TN_OK;
 }
 
-// ---- layout pre-pass ------------------------------------------------------
-// Decides, for a whole flat replace-left path, the order each step stores
-// its output in. Today's rule is the symmetric difference of the operands'
+// ---- walk plan ------------------------------------------------------------
+// Everything about a whole flat replace-left path that follows from the path
+// alone: the order each step stores its output in, and which operands of
+// each step are packed one step early (the look-ahead pack).
+//
+// Stored orders. Today's rule is the symmetric difference of the operands'
 // stored orders. When the next step c = s+1 reads step s's output as its A
-// operand and would have to pack it inline (the one operand the prepack
+// operand and would have to pack it inline (the one operand the look-ahead
 // cannot hide: it does not exist while step s-1 runs), step s stores
 //   [M' legs][K' legs]      M' = legs c keeps, K' = legs c contracts
 // instead, provided plan_step admits that order to the scatter epilogue.
@@ -592,16 +596,36 @@ inline int plan_step(bool c128, const u64* out_labels, const u64* out_shape,
 // An output read as a B operand is left alone: its K' order is dictated by
 // the other operand. The last step stores today's order, so results keep
 // their legs. Slot labels always are the stored order.
+//
+// Look-ahead packs. While step s-1's GEMM runs (MFMA-bound, <10% of the HBM
+// bandwidth a permute needs) the walk may pack step s's GEMM operands on a
+// second stream, so that step s finds them ready. The rule, stated here
+// once: step s is TTGT and not gather_gemm, and an operand is packed early
+// iff the step's plan packs it and step s-1 did not produce it (it does not
+// exist yet while s-1 runs). A prepacked slot is consumed by the very next
+// step, so the orders this sweep sees are the orders the walk finds: the
+// decision is a function of the path. Whether the walk acts on it (switch,
+// arena, second stream, the allocations succeeding) is decided at run time;
+// dispatch plans from the operands as they then sit on the device.
 
 struct LayoutTensor {
   std::vector<u64> labels, dims;
 };
 
+// operands of one step that are packed while the previous step runs
+struct EarlyPack {
+  bool a = false, b = false;
+  std::vector<int> a_axes, b_axes;  // axis orders of the packed layouts
+  u64 a_elems = 0, b_elems = 0;     // m*k, k*n
+};
+
 struct LayoutPlan {
-  bool valid = false;  // false: the walk uses the symmetric difference
+  bool valid = false;  // false: no plan, `err` says why; the walk refuses
+  std::string err;
   std::vector<LayoutTensor> out;  // stored order of every step's output
   std::vector<int32_t> scatter_out;
-  std::vector<u64> inline_pack_bytes;
+  std::vector<EarlyPack> early;   // look-ahead pack of every step
+  std::vector<u64> inline_pack_bytes;  // what the step packs, minus `early`
 };
 
 inline bool layout_has(const LayoutTensor& t, u64 lab) {
@@ -627,7 +651,9 @@ inline void layout_symdiff(const LayoutTensor& a, const LayoutTensor& b,
     }
 }
 
-inline void layout_meta(const LayoutTensor& t, Meta* m) {
+// Meta of a contiguous row-major tensor with these labels and dims
+inline void layout_meta(const LayoutTensor& t, Meta* m,
+                        const void* data = nullptr) {
   m->nd = (int)t.labels.size();
   i64 stride = 1;
   for (int x = m->nd - 1; x >= 0; --x) {
@@ -636,19 +662,20 @@ inline void layout_meta(const LayoutTensor& t, Meta* m) {
     m->strides[x] = stride;
     stride *= (i64)t.dims[x];
   }
-  m->data = nullptr;
+  m->data = data;
 }
 
 inline bool layout_plan_step(bool c128, const LayoutTensor& out,
                              const LayoutTensor& a, const LayoutTensor& b,
-                             bool has_stream2, StepPlan* p) {
+                             bool has_stream2, StepPlan* p,
+                             std::string* err = nullptr) {
   Meta ma, mb;
-  std::string err;
+  std::string local;
   layout_meta(a, &ma);
   layout_meta(b, &mb);
   return plan_step(c128, out.labels.data(), out.dims.data(),
                    (int)out.labels.size(), ma, mb, has_stream2, p,
-                   &err) == TN_OK;
+                   err ? err : &local) == TN_OK;
 }
 
 inline void plan_layouts(bool c128, const std::vector<LayoutTensor>& leaves,
@@ -663,15 +690,19 @@ inline void plan_layouts(bool c128, const std::vector<LayoutTensor>& leaves,
   std::vector<char> alive(n, 1);
   std::vector<long> producer(n, -1), consumer(nsteps, -1);
   std::vector<char> cons_as_a(nsteps, 0);
+  auto refuse = [&](const char* why) { lp->err = why; };
+  const char* const rank_err = "tensor rank exceeds 40";
+  static_assert(TN_MAXR == 40, "rank_err names TN_MAXR");
   for (const LayoutTensor& t : leaves)
-    if (t.labels.size() > (size_t)TN_MAXR) return;
+    if (t.labels.size() > (size_t)TN_MAXR) return refuse(rank_err);
   for (size_t s = 0; s < nsteps; ++s) {
     const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
-    if (i >= n || j >= n || i == j || !alive[i] || !alive[j]) return;
+    if (i >= n || j >= n || i == j || !alive[i] || !alive[j])
+      return refuse("invalid contraction path step");
     can_a[s] = canon[i];
     can_b[s] = canon[j];
     layout_symdiff(canon[i], canon[j], &can_out[s]);
-    if (can_out[s].labels.size() > (size_t)TN_MAXR) return;
+    if (can_out[s].labels.size() > (size_t)TN_MAXR) return refuse(rank_err);
     if (producer[i] >= 0) {
       consumer[producer[i]] = (long)s;
       cons_as_a[producer[i]] = 1;
@@ -715,14 +746,22 @@ inline void plan_layouts(bool c128, const std::vector<LayoutTensor>& leaves,
   std::vector<LayoutTensor> stored(leaves);
   lp->out.resize(nsteps);
   lp->scatter_out.assign(nsteps, 0);
+  lp->early.assign(nsteps, EarlyPack());
   lp->inline_pack_bytes.assign(nsteps, 0);
+  // the look-ahead pack of step s under plan p: the rule of the comment above
+  auto early_of = [&](size_t s, const StepPlan& p) {
+    EarlyPack e;
+    if (s == 0 || p.route != TN_ROUTE_TTGT || p.gather_gemm) return e;
+    const u64 made = pairs[2 * (s - 1)];  // slot step s-1 stored its output in
+    e.a = p.pack_a && pairs[2 * s] != made;
+    e.b = p.pack_b && pairs[2 * s + 1] != made;
+    return e;
+  };
   auto inline_bytes = [&](size_t s, const StepPlan& p) -> u64 {
     if (p.route != TN_ROUTE_TTGT || p.gather_gemm) return 0;
-    // an operand the previous step produced cannot have been prepacked
-    const bool a_new = s == 0 || pairs[2 * s] == pairs[2 * (s - 1)];
-    const bool b_new = s == 0 || pairs[2 * s + 1] == pairs[2 * (s - 1)];
-    return ((p.pack_a && a_new) ? p.m * p.k * esize : 0) +
-           ((p.pack_b && b_new) ? p.k * p.n * esize : 0);
+    const EarlyPack e = early_of(s, p);
+    return ((p.pack_a && !e.a) ? p.m * p.k * esize : 0) +
+           ((p.pack_b && !e.b) ? p.k * p.n * esize : 0);
   };
   for (size_t s = 0; s < nsteps; ++s) {
     const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
@@ -730,11 +769,11 @@ inline void plan_layouts(bool c128, const std::vector<LayoutTensor>& leaves,
     LayoutTensor base;
     layout_symdiff(A, B, &base);
     StepPlan pb;
-    if (!layout_plan_step(c128, base, A, B, true, &pb)) return;
+    if (!layout_plan_step(c128, base, A, B, true, &pb, &lp->err)) return;
     LayoutTensor chosen = consumer[s] < 0 ? can_out[s] : base;
     StepPlan pc = pb;
     if (consumer[s] < 0 && chosen.labels != base.labels &&
-        !layout_plan_step(c128, chosen, A, B, true, &pc))
+        !layout_plan_step(c128, chosen, A, B, true, &pc, &lp->err))
       return;
     if (!want[s].labels.empty()) {
       // would step s+1 pack this output inline under today's order?
@@ -752,6 +791,11 @@ inline void plan_layouts(bool c128, const std::vector<LayoutTensor>& leaves,
         pc = pw;
       }
     }
+    EarlyPack& e = lp->early[s] = early_of(s, pc);
+    if (e.a) e.a_axes.assign(pc.a_axes.begin(), pc.a_axes.end());
+    if (e.b) e.b_axes.assign(pc.b_axes.begin(), pc.b_axes.end());
+    e.a_elems = e.a ? pc.m * pc.k : 0;
+    e.b_elems = e.b ? pc.k * pc.n : 0;
     lp->scatter_out[s] = pc.scatter_out;
     lp->inline_pack_bytes[s] = inline_bytes(s, pc);
     lp->out[s] = chosen;

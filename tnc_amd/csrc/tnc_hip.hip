@@ -1511,9 +1511,10 @@ struct Arena {
 struct WsCtx {
   Arena* arena = nullptr;  // optional
   hipStream_t stream = nullptr;
-  // stream-capture mode (hipGraph): non-arena allocations poison the graph
-  // (their pointers would dangle on replay) and frees must be deferred past
-  // EndCapture (hipFree device-syncs, which is illegal mid-capture)
+  // stream-capture mode (hipGraph): non-arena allocations are refused and
+  // poison the graph (hipMalloc is illegal mid-capture, and its pointers
+  // would dangle on replay); frees must be deferred past EndCapture (hipFree
+  // device-syncs, which is illegal mid-capture)
   bool capturing = false;
   bool spilled = false;
   std::vector<void*>* deferred = nullptr;
@@ -1536,7 +1537,15 @@ static int ws_alloc(WsCtx& ctx, void** p, size_t bytes) {
     *p = ctx.arena->alloc(bytes);
     if (*p) return TN_OK;
   }
-  if (ctx.capturing) ctx.spilled = true;
+  if (ctx.capturing) {
+    // Outside the arena there is only hipMalloc, which a thread may not call
+    // while its stream captures: the runtime invalidates the capture and the
+    // stream stays in capture mode past EndCapture. Report the spill; the
+    // caller drops this capture and runs normally.
+    ctx.spilled = true;
+    g_last_error = "arena exhausted under stream capture";
+    return TN_ERR_OOM;
+  }
   if (hipMalloc(p, bytes) != hipSuccess) {
     (void)hipGetLastError();  // don't leave a sticky OOM for launch checks
     size_t fb = 0, tb = 0;
@@ -1645,6 +1654,14 @@ static int launch_permute(const CT* src, CT* dst, u64 elems,
   HIP_CHECK(hipGetLastError());
   return TN_OK;
 }
+
+// Instantiated here, ahead of the einsum templates: the order in which the
+// kernel templates are first used fixes their order in the code object, and
+// the permute kernels come first in it.
+template int launch_permute(const double2*, double2*, u64,
+                            const std::vector<AxisInfo>&, hipStream_t);
+template int launch_permute(const float2*, float2*, u64,
+                            const std::vector<AxisInfo>&, hipStream_t);
 
 // ---------------------------------------------------------------------------
 // core einsum over device buffers; out is contiguous row-major in out order.
@@ -2270,9 +2287,8 @@ extern "C" int tn_einsum_c64(const u64* out_labels, const u64* out_shape,
 // network executor (contract_tensor_network replacement)
 // ---------------------------------------------------------------------------
 
-struct DevTensor {
-  std::vector<u64> labels;
-  std::vector<u64> dims;
+// labels and dims in stored order, contiguous row-major on the device
+struct DevTensor : LayoutTensor {
   void* data = nullptr;
   u64 elems = 1;
   bool owned = false;     // intermediate owned by the walk (freed on consume)
@@ -2298,7 +2314,8 @@ struct tn_net {
   // reserved). Invalidated by a different path or new leaves.
   hipGraphExec_t graph_exec = nullptr;
   std::vector<u64> graph_pairs;
-  // stored out order of every step (plan_layouts), kept per path
+  // the walk plan (plan_layouts): stored out order and look-ahead pack of
+  // every step, kept per path
   LayoutPlan layout;
   std::vector<u64> layout_pairs;
   bool layout_known = false;
@@ -2409,419 +2426,339 @@ extern "C" int64_t tn_net_add_leaf_dev(tn_net* net, const u64* labels,
   return (int64_t)net->leaves.size() - 1;
 }
 
-// out legs of one step = symmetric difference, A-only legs in A order then
-// B-only in B order (tensor.rs:709-725) — the executor's layout contract
-// wherever the layout pre-pass (plan_layouts) has not chosen another order.
-static void symdiff(const DevTensor& a, const DevTensor& b,
-                    std::vector<u64>* labels, std::vector<u64>* dims) {
-  for (size_t i = 0; i < a.labels.size(); ++i) {
-    bool shared = false;
-    for (u64 bl : b.labels)
-      if (bl == a.labels[i]) shared = true;
-    if (!shared) {
-      labels->push_back(a.labels[i]);
-      dims->push_back(a.dims[i]);
-    }
-  }
-  for (size_t i = 0; i < b.labels.size(); ++i) {
-    bool shared = false;
-    for (u64 al : a.labels)
-      if (al == b.labels[i]) shared = true;
-    if (!shared) {
-      labels->push_back(b.labels[i]);
-      dims->push_back(b.dims[i]);
-    }
-  }
+// release the previous final tensor. Never inside a stream capture: the
+// release may hipFree, and hipFree device-syncs.
+static void release_final(tn_net* net) {
+  if (!net->has_final || !net->final_t.owned) return;
+  if (net->final_in_arena)
+    net->arena.release(net->final_t.data);
+  else
+    (void)hipFree(net->final_t.data);
+  net->final_t = DevTensor();
+  net->has_final = false;
+  net->final_in_arena = false;
 }
 
-// ---- pack-overlap planning ------------------------------------------------
-// Would the step take the TTGT route, and which operands would it pack? Asked
-// of the same planner the dispatch uses. The walk pre-permutes the NEXT
-// step's GEMM operands on a second stream while the current step's GEMM runs
-// (the GEMMs are MFMA-bound and use <10% of the HBM bandwidth the permutes
-// need, so the packs ride along ~free). A prepacked operand is a valid
-// contiguous tensor in pack order, which the step then finds ready; an
-// operand NOT prepacked is packed inline as before.
-struct PackPlan {
-  bool packA = false, packB = false;
-  std::vector<int> a_axes, b_axes;  // axis orders of the packed layouts
-  u64 MK = 0, KN = 0;               // packed element counts
-};
-
-static bool plan_prepack(const Meta& A, const Meta& B, const u64* out_labels,
-                         const u64* out_shape, int out_nd, PackPlan* plan,
-                         bool c128) {
-  StepPlan p;
-  std::string err;
-  // (no second stream: the pipeline choice has no bearing on what packs)
-  if (plan_step(c128, out_labels, out_shape, out_nd, A, B, false, &p, &err) !=
-          TN_OK ||
-      p.route != TN_ROUTE_TTGT || p.gather_gemm)
-    return false;
-  plan->packA = p.pack_a;
-  plan->packB = p.pack_b;
-  plan->a_axes.assign(p.a_axes.begin(), p.a_axes.end());
-  plan->b_axes.assign(p.b_axes.begin(), p.b_axes.end());
-  plan->MK = p.m * p.k;
-  plan->KN = p.k * p.n;
-  return plan->packA || plan->packB;
-}
-
-// fill a Meta from a contiguous row-major DevTensor
-static void meta_of(const DevTensor& t, Meta* m) {
-  m->nd = (int)t.labels.size();
-  for (int x = 0; x < m->nd; ++x) {
-    m->labels[x] = t.labels[x];
-    m->dims[x] = t.dims[x];
-  }
-  i64 stride = 1;
-  for (int x = m->nd - 1; x >= 0; --x) {
-    m->strides[x] = stride;
-    stride *= (i64)m->dims[x];
-  }
-  m->data = t.data;
-}
-
-static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
-                         double* step_ms, double* gemm_ms, int32_t* kind,
-                         double* elapsed_ms, bool capture = false,
-                         std::vector<void*>* deferred = nullptr,
-                         bool* spilled = nullptr) {
-  if (!net) FAILV(TN_ERR_INVALID, "null net");
-  HIP_CHECK(hipSetDevice(net->device));
-  WsCtx ws{net->arena.base ? &net->arena : nullptr, net->stream, capture,
-           false, deferred};
-  ws.stream2 = net->stream2;
-  if (net->has_final && net->final_t.owned) {
-    if (net->final_in_arena)
-      net->arena.release(net->final_t.data);
-    else
-      (void)hipFree(net->final_t.data);
-    net->final_t = DevTensor();
-    net->has_final = false;
-    net->final_in_arena = false;
-  }
-  size_t n = net->leaves.size();
-  std::vector<DevTensor> slots(net->leaves);  // shallow copies; owned=false
-  for (auto& s : slots) s.owned = false;
-  std::vector<char> alive(n, 1);
-
-  bool profiled = (step_ms != nullptr);
-  std::vector<hipEvent_t> ev;
-  std::vector<int> kinds_local;
-  if (profiled) {
-    ev.resize(4 * nsteps);  // step start/end + gemm start/end
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-    kinds_local.assign(nsteps, 0);
-  }
-
-  double t0_ms = 0.0;
-  hipEvent_t walk_start = nullptr, walk_end = nullptr;
-  if (!capture) {
-    HIP_CHECK(hipStreamSynchronize(net->stream));
-    HIP_CHECK(hipEventCreate(&walk_start));
-    HIP_CHECK(hipEventCreate(&walk_end));
-    HIP_CHECK(hipEventRecord(walk_start, net->stream));
-  }
-
-  int rc = TN_OK;
-  // pack-overlap state: while step s runs on net->stream, the NEXT step's
-  // GEMM pack permutes run on net->stream2 (after an event marking steps
-  // < s complete). The replaced originals are freed at the top of step s+1,
-  // after the main stream waits on the packs — so every arena block's
-  // next user is ordered behind its last reader, preserving the arena's
-  // stream-ordered reuse contract across both streams.
-  struct Pending {
-    void* old_data;
-    bool old_owned;
-  };
-  std::vector<Pending> pending;
-  hipEvent_t pending_done = nullptr;
-  std::vector<hipEvent_t> prep_events;
-  ws.events = &prep_events;  // pipeline events: destroyed after the walk
-  const bool overlap =
-      !env_switch(ENV_NO_PREPACK) && net->stream2 && net->arena.base != nullptr;
-
-  // stored order of every step's output, decided once per path
+// the walk plan of this path over the net's leaves, computed once per path
+static const LayoutPlan& walk_plan(tn_net* net, const u64* pairs,
+                                   size_t nsteps) {
   if (!net->layout_known || net->layout_pairs.size() != 2 * nsteps ||
       !std::equal(net->layout_pairs.begin(), net->layout_pairs.end(), pairs)) {
-    std::vector<LayoutTensor> lt(n);
-    for (size_t x = 0; x < n; ++x) {
-      lt[x].labels = net->leaves[x].labels;
-      lt[x].dims = net->leaves[x].dims;
-    }
+    const std::vector<LayoutTensor> lt(net->leaves.begin(), net->leaves.end());
     plan_layouts(net->dtype == 0, lt, pairs, nsteps, &net->layout);
     net->layout_pairs.assign(pairs, pairs + 2 * nsteps);
     net->layout_known = true;
   }
-  const LayoutPlan& layout = net->layout;
-  // out legs of step s with operands a, b (an invalid path has no plan; the
-  // walk reports it)
-  auto out_order = [&](size_t s, const DevTensor& a, const DevTensor& b,
-                       std::vector<u64>* labels, std::vector<u64>* dims) {
-    if (layout.valid) {
-      *labels = layout.out[s].labels;
-      *dims = layout.out[s].dims;
-    } else {
-      symdiff(a, b, labels, dims);
-    }
-  };
+  return net->layout;
+}
 
-  for (size_t s = 0; s < nsteps; ++s) {
-    u64 i = pairs[2 * s], j = pairs[2 * s + 1];
-    if (i >= n || j >= n || !alive[i] || !alive[j] || i == j) {
-      rc = TN_ERR_INVALID;
-      g_last_error = "invalid contraction path step";
-      break;
+// the one place the walk switches on dtype: f gets a null CT* as a type tag
+template <typename F>
+static int with_dtype(int dtype, F&& f) {
+  return dtype == 0 ? f((double2*)nullptr) : f((float2*)nullptr);
+}
+
+// per-step outputs of a profiled walk (step_ms null: a plain walk)
+struct StepTimes {
+  double* step_ms = nullptr;
+  double* gemm_ms = nullptr;
+  int32_t* kind = nullptr;
+};
+
+// what a walk under stream capture leaves for after EndCapture
+struct CaptureLog {
+  std::vector<void*> deferred;  // non-arena blocks to hipFree
+  bool spilled = false;         // a block came from outside the arena
+};
+
+// One contraction's transient state. The destructor gives back whatever the
+// walk still holds, so every exit from contract_impl and from the pieces
+// below is a plain return.
+//
+// Pack overlap: while step s runs on net->stream, the NEXT step's GEMM pack
+// permutes run on net->stream2 (after an event marking steps < s complete).
+// A prepacked slot becomes a contiguous tensor in pack order, which the step
+// then finds ready; an operand not prepacked is packed inline. The replaced
+// originals are freed at the top of step s+1, after the main stream waits on
+// the packs — so every arena block's next user is ordered behind its last
+// reader, preserving the arena's stream-ordered reuse contract across both
+// streams.
+struct Walk {
+  tn_net* const net;
+  CaptureLog* const cap;  // null: a normal run
+  WsCtx ws;
+  std::vector<DevTensor> slots;  // the leaves (not owned), then intermediates
+  std::vector<char> alive;
+  DevTensor out;                 // the current step's output, until retired
+  std::vector<void*> pending;    // owned originals a prepack replaced
+  hipEvent_t pending_done = nullptr;  // the packs of `pending` have run
+  // every event of the walk, the pack pipeline's included (ws.events);
+  // destroyed when the walk is over
+  std::vector<hipEvent_t> events;
+  std::vector<hipEvent_t> prof_ev;  // per step: start, end, gemm start, end
+  hipEvent_t walk_start = nullptr, walk_end = nullptr;
+  const bool overlap;
+  bool done = false;  // the final tensor was handed over
+
+  Walk(tn_net* n, CaptureLog* c)
+      : net(n), cap(c),
+        ws{n->arena.base ? &n->arena : nullptr, n->stream, c != nullptr, false,
+           c ? &c->deferred : nullptr},
+        slots(n->leaves), alive(n->leaves.size(), 1),
+        overlap(!env_switch(ENV_NO_PREPACK) && n->stream2 &&
+                n->arena.base != nullptr) {
+    ws.stream2 = n->stream2;
+    ws.events = &events;
+    for (auto& s : slots) s.owned = false;  // shallow copies
+  }
+  Walk(const Walk&) = delete;
+
+  ~Walk() {
+    if (!done && !cap) {
+      (void)hipStreamSynchronize(net->stream);
+      (void)hipStreamSynchronize(net->stream2);
     }
-    // join this step's prepack (issued during step s-1): the packed
-    // operands replace slots[i]/slots[j]; free the originals only now,
-    // behind the wait, so their blocks cannot be re-handed while the pack
-    // kernels still read them
-    if (pending_done) {
-      if (hipStreamWaitEvent(net->stream, pending_done, 0) != hipSuccess) {
-        rc = TN_ERR_HIP;
-        g_last_error = "hipStreamWaitEvent failed (prepack join)";
-        break;
-      }
-      for (auto& p : pending)
-        if (p.old_owned && p.old_data) ws_free(ws, p.old_data);
-      pending.clear();
-      pending_done = nullptr;
+    // left by an early exit: deferred originals, the current out, owned
+    // intermediates
+    for (void* p : pending) ws_free(ws, p);
+    if (out.owned) ws_free(ws, out.data);
+    for (size_t x = 0; x < slots.size(); ++x)
+      if (alive[x] && slots[x].owned) ws_free(ws, slots[x].data);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    if (cap) cap->spilled = ws.spilled;
+  }
+
+  hipEvent_t new_event() {
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+    events.push_back(e);
+    return e;
+  }
+
+  int begin(size_t nsteps, bool profiled) {
+    for (size_t x = 0; profiled && x < 4 * nsteps; ++x) {
+      prof_ev.push_back(new_event());
+      if (!prof_ev.back()) FAILV(TN_ERR_HIP, "hipEventCreate failed");
     }
-    DevTensor& A = slots[i];
-    DevTensor& B = slots[j];
-    DevTensor out;
-    out_order(s, A, B, &out.labels, &out.dims);
-    out.elems = 1;
+    if (cap) return TN_OK;
+    HIP_CHECK(hipStreamSynchronize(net->stream));
+    walk_start = new_event();
+    walk_end = new_event();
+    if (!walk_start || !walk_end) FAILV(TN_ERR_HIP, "hipEventCreate failed");
+    HIP_CHECK(hipEventRecord(walk_start, net->stream));
+    return TN_OK;
+  }
+
+  // join this step's prepack (issued during the step before): free the
+  // replaced originals only now, behind the wait, so their blocks cannot be
+  // re-handed while the pack kernels still read them
+  int join_prepack() {
+    if (!pending_done) return TN_OK;
+    if (hipStreamWaitEvent(net->stream, pending_done, 0) != hipSuccess)
+      FAILV(TN_ERR_HIP, "hipStreamWaitEvent failed (prepack join)");
+    for (void* p : pending) ws_free(ws, p);
+    pending.clear();
+    pending_done = nullptr;
+    return TN_OK;
+  }
+
+  int alloc_out(const LayoutTensor& order) {
+    out = DevTensor();
+    out.labels = order.labels;
+    out.dims = order.dims;
     for (u64 d : out.dims) out.elems *= d;
-    if (ws_alloc(ws, (void**)&out.data, out.elems * net->esize) != TN_OK) {
-      rc = TN_ERR_OOM;
-      g_last_error = "device allocation failed for intermediate";
-      break;
+    if (ws_alloc(ws, &out.data, out.elems * net->esize) != TN_OK) {
+      out.data = nullptr;
+      FAILV(TN_ERR_OOM, "device allocation failed for intermediate");
     }
     out.owned = true;
+    return TN_OK;
+  }
 
-    // prepack the next step's GEMM operands on stream2 (overlaps this
-    // step's kernels). A prepacked slot becomes a contiguous tensor in
-    // pack order — einsum_dev_impl then sees is_ready and skips its
-    // inline pack. Arena-only; on any shortage the step simply packs
-    // inline as before.
-    if (overlap && s + 1 < nsteps) {
-      u64 ni = pairs[2 * (s + 1)], nj = pairs[2 * (s + 1) + 1];
-      bool valid = ni < n && nj < n && ni != nj && ni != j && nj != j &&
-                   (ni == i || alive[ni]) && (nj == i || alive[nj]);
-      if (valid) {
-        const DevTensor& TA = (ni == i) ? out : slots[ni];
-        const DevTensor& TB = (nj == i) ? out : slots[nj];
-        std::vector<u64> nlabels, ndims;
-        out_order(s + 1, TA, TB, &nlabels, &ndims);
-        Meta mna, mnb;
-        PackPlan plan;
-        if ((int)TA.labels.size() <= TN_MAXR &&
-            (int)TB.labels.size() <= TN_MAXR &&
-            (int)nlabels.size() <= TN_MAXR) {
-          meta_of(TA, &mna);
-          meta_of(TB, &mnb);
-          if (plan_prepack(mna, mnb, nlabels.data(), ndims.data(),
-                           (int)nlabels.size(), &plan,
-                           net->dtype == 0)) {
-            void* dstA = nullptr;
-            void* dstB = nullptr;
-            bool wantA = plan.packA && ni != i;
-            bool wantB = plan.packB && nj != i;
-            if (wantA) dstA = net->arena.alloc(plan.MK * net->esize);
-            if (wantB) dstB = net->arena.alloc(plan.KN * net->esize);
-            if ((wantA && !dstA) || (wantB && !dstB)) {
-              // partial shortage: keep it simple, pack inline at s+1
-              if (dstA) net->arena.release(dstA);
-              if (dstB) net->arena.release(dstB);
-              dstA = dstB = nullptr;
-            }
-            if (dstA || dstB) {
-              hipEvent_t e_ready = nullptr, e_done = nullptr;
-              if (hipEventCreate(&e_ready) != hipSuccess) e_ready = nullptr;
-              if (e_ready && hipEventCreate(&e_done) != hipSuccess) {
-                (void)hipEventDestroy(e_ready);
-                e_ready = nullptr;
-              }
-              if (!e_ready) {
-                if (dstA) net->arena.release(dstA);
-                if (dstB) net->arena.release(dstB);
-              } else {
-                prep_events.push_back(e_ready);
-                prep_events.push_back(e_done);
-                if (hipEventRecord(e_ready, net->stream) != hipSuccess ||
-                    hipStreamWaitEvent(net->stream2, e_ready, 0) !=
-                        hipSuccess) {
-                  rc = TN_ERR_HIP;
-                  g_last_error = "prepack event sync failed";
-                  break;
-                }
-                auto do_pack = [&](DevTensor& S, void* dst,
-                                   const std::vector<int>& axes,
-                                   u64 elems) -> int {
-                  Meta ms;
-                  meta_of(S, &ms);
-                  std::vector<AxisInfo> ax;
-                  for (int axis : axes)
-                    ax.push_back({ms.dims[axis], ms.strides[axis], 0});
-                  int prc =
-                      net->dtype == 0
-                          ? launch_permute((const double2*)S.data,
-                                           (double2*)dst, elems, ax,
-                                           net->stream2)
-                          : launch_permute((const float2*)S.data,
-                                           (float2*)dst, elems, ax,
-                                           net->stream2);
-                  if (prc != TN_OK) return prc;
-                  pending.push_back({S.owned ? S.data : nullptr, S.owned});
-                  std::vector<u64> nl, nd;
-                  for (int axis : axes) {
-                    nl.push_back(S.labels[axis]);
-                    nd.push_back(S.dims[axis]);
-                  }
-                  S.labels = std::move(nl);
-                  S.dims = std::move(nd);
-                  S.data = dst;
-                  S.owned = true;
-                  S.external = false;
-                  return TN_OK;
-                };
-                if (dstA) rc = do_pack(slots[ni], dstA, plan.a_axes, plan.MK);
-                if (rc == TN_OK && dstB)
-                  rc = do_pack(slots[nj], dstB, plan.b_axes, plan.KN);
-                if (rc != TN_OK) break;
-                if (hipEventRecord(e_done, net->stream2) != hipSuccess) {
-                  rc = TN_ERR_HIP;
-                  g_last_error = "prepack event record failed";
-                  break;
-                }
-                pending_done = e_done;
-              }
-            }
-          }
-        }
-      }
+  // pack slot S into *dst in the given axis order on stream2; S adopts *dst
+  int pack_slot(DevTensor& S, const std::vector<int>& axes, u64 elems,
+                void** dst) {
+    Meta ms;
+    layout_meta(S, &ms, S.data);
+    std::vector<AxisInfo> ax;
+    LayoutTensor packed;
+    for (int axis : axes) {
+      ax.push_back({ms.dims[axis], ms.strides[axis], 0});
+      packed.labels.push_back(S.labels[axis]);
+      packed.dims.push_back(S.dims[axis]);
     }
+    int rc = with_dtype(net->dtype, [&](auto* t) {
+      typedef std::remove_pointer_t<decltype(t)> CT;
+      return launch_permute((const CT*)S.data, (CT*)*dst, elems, ax,
+                            net->stream2);
+    });
+    if (rc != TN_OK) return rc;
+    if (S.owned) pending.push_back(S.data);
+    static_cast<LayoutTensor&>(S) = std::move(packed);
+    S.data = *dst;
+    S.owned = true;
+    S.external = false;
+    *dst = nullptr;
+    return TN_OK;
+  }
 
+  // the two events, then the packs on stream2 behind all the main stream
+  // has been given so far; without events the step packs inline
+  int launch_prepack(const EarlyPack& e, u64 ni, u64 nj, void* dst[2]) {
+    hipEvent_t ready = new_event();
+    hipEvent_t packed = ready ? new_event() : nullptr;
+    if (!packed) return TN_OK;
+    if (hipEventRecord(ready, net->stream) != hipSuccess ||
+        hipStreamWaitEvent(net->stream2, ready, 0) != hipSuccess)
+      FAILV(TN_ERR_HIP, "prepack event sync failed");
+    int rc = TN_OK;
+    if (e.a) rc = pack_slot(slots[ni], e.a_axes, e.a_elems, &dst[0]);
+    if (rc == TN_OK && e.b)
+      rc = pack_slot(slots[nj], e.b_axes, e.b_elems, &dst[1]);
+    if (rc != TN_OK) return rc;
+    if (hipEventRecord(packed, net->stream2) != hipSuccess)
+      FAILV(TN_ERR_HIP, "prepack event record failed");
+    pending_done = packed;
+    return TN_OK;
+  }
+
+  // Act on the planned look-ahead pack of the next step (operands ni, nj),
+  // overlapping this step's kernels. Arena only, both buffers or none; on
+  // any shortage the step simply packs inline.
+  int issue_prepack(const EarlyPack& e, u64 ni, u64 nj) {
+    if (!overlap || !(e.a || e.b)) return TN_OK;
+    Arena& arena = net->arena;
+    void* dst[2] = {e.a ? arena.alloc(e.a_elems * net->esize) : nullptr,
+                    e.b ? arena.alloc(e.b_elems * net->esize) : nullptr};
+    int rc = TN_OK;
+    if ((!e.a || dst[0]) && (!e.b || dst[1]))
+      rc = launch_prepack(e, ni, nj, dst);
+    for (void* p : dst)  // not adopted by a slot: a shortage, or a failure
+      if (p) arena.release(p);
+    return rc;
+  }
+
+  // Plan and run step s on the operands as they sit on the device now
+  // (einsum_dev_impl: a failed prepack, or a prepacked A that turns the pack
+  // pipeline off, is its business).
+  int dispatch(size_t s, const DevTensor& A, const DevTensor& B,
+               const StepTimes& times) {
+    const bool profiled = !prof_ev.empty();
     Meta ma, mb;
-    meta_of(A, &ma);
-    meta_of(B, &mb);
-
-    if (profiled) HIP_CHECK(hipEventRecord(ev[4 * s], net->stream));
-    StepStats st;
+    layout_meta(A, &ma, A.data);
+    layout_meta(B, &mb, B.data);
+    StepStats st{};
     if (profiled) {
-      st.gemm_ev0 = ev[4 * s + 2];
-      st.gemm_ev1 = ev[4 * s + 3];
+      HIP_CHECK(hipEventRecord(prof_ev[4 * s], net->stream));
+      st.gemm_ev0 = prof_ev[4 * s + 2];
+      st.gemm_ev1 = prof_ev[4 * s + 3];
     }
-    if (net->dtype == 0)
-      rc = einsum_dev_impl<double2>(out.labels.data(), out.dims.data(),
-                                    (int)out.labels.size(), ma, mb,
-                                    (double2*)out.data, net->stream, ws, &st);
-    else
-      rc = einsum_dev_impl<float2>(out.labels.data(), out.dims.data(),
-                                   (int)out.labels.size(), ma, mb,
-                                   (float2*)out.data, net->stream, ws, &st);
-    if (profiled) HIP_CHECK(hipEventRecord(ev[4 * s + 1], net->stream));
-    if (kind) kind[s] = st.kind;
-    if (profiled) kinds_local[s] = st.kind;
+    int rc = with_dtype(net->dtype, [&](auto* t) {
+      typedef std::remove_pointer_t<decltype(t)> CT;
+      return einsum_dev_impl<CT>(out.labels.data(), out.dims.data(),
+                                 (int)out.labels.size(), ma, mb, (CT*)out.data,
+                                 net->stream, ws, &st);
+    });
+    if (profiled) HIP_CHECK(hipEventRecord(prof_ev[4 * s + 1], net->stream));
+    if (times.kind) times.kind[s] = st.kind;
+    // only TTGT steps (kind 2/3) record the gemm events; probing unrecorded
+    // events would fail AND leave a sticky TLS error
+    if (profiled && st.kind != 2 && st.kind != 3) prof_ev[4 * s + 2] = nullptr;
     if (rc != TN_OK) {
       char buf[96];
       snprintf(buf, sizeof buf, " (at step %zu, out elems %llu)", s,
                (unsigned long long)out.elems);
       g_last_error += buf;
-      ws_free(ws, out.data);
-      break;
     }
-    // free consumed intermediates (leaves persist)
-    if (A.owned) ws_free(ws, A.data);
-    if (B.owned) ws_free(ws, B.data);
+    return rc;
+  }
+
+  // free consumed intermediates (leaves persist); out takes A's slot
+  void retire(u64 i, u64 j) {
+    if (slots[i].owned) ws_free(ws, slots[i].data);
+    if (slots[j].owned) ws_free(ws, slots[j].data);
     slots[i] = std::move(out);
+    out = DevTensor();
     alive[j] = 0;
   }
 
-  if (!capture) {
-    HIP_CHECK(hipEventRecord(walk_end, net->stream));
-    HIP_CHECK(hipStreamSynchronize(net->stream));
-  }
-  if (rc == TN_OK) {
+  // close the timed span and read the timings back
+  int read_times(size_t nsteps, const StepTimes& times, double* elapsed_ms) {
     float ms = 0.f;
-    if (!capture) {
+    if (!cap) {
+      HIP_CHECK(hipEventRecord(walk_end, net->stream));
+      HIP_CHECK(hipStreamSynchronize(net->stream));
       HIP_CHECK(hipEventElapsedTime(&ms, walk_start, walk_end));
     }
-    if (elapsed_ms) *elapsed_ms = (double)ms + t0_ms;
-    if (profiled) {
-      for (size_t s = 0; s < nsteps; ++s) {
-        float sms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&sms, ev[4 * s], ev[4 * s + 1]));
-        step_ms[s] = (double)sms;
-        if (gemm_ms) {
-          float gms = 0.f;
-          // only TTGT steps (kind 2/3) record the gemm events; probing
-          // unrecorded events would fail AND leave a sticky TLS error
-          if ((kinds_local[s] == 2 || kinds_local[s] == 3) &&
-              hipEventElapsedTime(&gms, ev[4 * s + 2], ev[4 * s + 3]) ==
-                  hipSuccess)
-            gemm_ms[s] = (double)gms;
-          else
-            gemm_ms[s] = 0.0;
-        }
-      }
-      (void)hipGetLastError();  // clear any error from unrecorded-event reads
+    if (elapsed_ms) *elapsed_ms = (double)ms;
+    if (prof_ev.empty()) return TN_OK;
+    for (size_t s = 0; s < nsteps; ++s) {
+      float sms = 0.f, gms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&sms, prof_ev[4 * s], prof_ev[4 * s + 1]));
+      times.step_ms[s] = (double)sms;
+      if (prof_ev[4 * s + 2] &&
+          hipEventElapsedTime(&gms, prof_ev[4 * s + 2], prof_ev[4 * s + 3]) !=
+              hipSuccess)
+        gms = 0.f;
+      if (times.gemm_ms) times.gemm_ms[s] = (double)gms;
     }
-    // locate final tensor
-    int final_idx = -1;
-    int count = 0;
-    for (size_t x = 0; x < n; ++x)
-      if (alive[x]) {
-        final_idx = (int)x;
-        ++count;
-      }
-    if (count != 1) {
-      rc = TN_ERR_INVALID;
-      g_last_error = "path did not fully contract the network";
+    (void)hipGetLastError();  // clear any error from unrecorded-event reads
+    return TN_OK;
+  }
+
+  // the one tensor left becomes the net's final tensor
+  int hand_over() {
+    size_t x = 0;
+    while (!alive[x]) ++x;
+    DevTensor& f = slots[x];
+    if (f.owned) {
+      net->final_in_arena = ws.arena && ws.arena->owns(f.data);
+      net->final_t = std::move(f);
+      f.owned = false;
     } else {
-      DevTensor& f = slots[final_idx];
-      if (!f.owned) {
-        // final == a leaf (empty path): copy so result is stable
-        DevTensor c = f;
-        if (hipMalloc((void**)&c.data, f.elems * net->esize) != hipSuccess) {
-          rc = TN_ERR_OOM;
-          g_last_error = "hipMalloc failed for final copy";
-        } else {
-          HIP_CHECK(hipMemcpy(c.data, f.data, f.elems * net->esize,
-                              hipMemcpyDeviceToDevice));
-          c.owned = true;
-          net->final_t = std::move(c);
-          net->has_final = true;
-        }
-      } else {
-        net->final_in_arena = ws.arena && ws.arena->owns(f.data);
-        net->final_t = std::move(f);
-        net->has_final = true;
+      // final == a leaf (empty path): copy so result is stable
+      DevTensor c = f;
+      if (hipMalloc(&c.data, f.elems * net->esize) != hipSuccess)
+        FAILV(TN_ERR_OOM, "hipMalloc failed for final copy");
+      if (hipMemcpy(c.data, f.data, f.elems * net->esize,
+                    hipMemcpyDeviceToDevice) != hipSuccess) {
+        (void)hipFree(c.data);
+        FAILV(TN_ERR_HIP, "hipMemcpy failed for final copy");
       }
+      c.owned = true;
+      net->final_t = std::move(c);
     }
+    net->has_final = true;
+    done = true;
+    return TN_OK;
   }
-  if (rc != TN_OK) {
-    // free any owned intermediates left over, plus originals whose
-    // prepack-deferred frees never ran
-    if (!capture) {
-      (void)hipStreamSynchronize(net->stream);
-      (void)hipStreamSynchronize(net->stream2);
-    }
-    for (auto& p : pending)
-      if (p.old_owned && p.old_data) ws_free(ws, p.old_data);
-    for (size_t x = 0; x < n; ++x)
-      if (alive[x] && slots[x].owned && slots[x].data)
-        ws_free(ws, slots[x].data);
+};
+
+static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
+                         const StepTimes& times, double* elapsed_ms,
+                         CaptureLog* cap = nullptr) {
+  if (!net) FAILV(TN_ERR_INVALID, "null net");
+  HIP_CHECK(hipSetDevice(net->device));
+  release_final(net);
+  const LayoutPlan& plan = walk_plan(net, pairs, nsteps);
+  if (!plan.valid) FAILV(TN_ERR_INVALID, "%s", plan.err.c_str());
+  if (net->leaves.size() != nsteps + 1)
+    FAILV(TN_ERR_INVALID, "path did not fully contract the network");
+  Walk w(net, cap);
+  if (int rc = w.begin(nsteps, times.step_ms != nullptr)) return rc;
+  for (size_t s = 0; s < nsteps; ++s) {
+    const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
+    int rc = w.join_prepack();
+    if (rc == TN_OK) rc = w.alloc_out(plan.out[s]);
+    if (rc == TN_OK && s + 1 < nsteps)
+      rc = w.issue_prepack(plan.early[s + 1], pairs[2 * s + 2],
+                           pairs[2 * s + 3]);
+    if (rc == TN_OK) rc = w.dispatch(s, w.slots[i], w.slots[j], times);
+    if (rc != TN_OK) return rc;
+    w.retire(i, j);
   }
-  if (spilled) *spilled = ws.spilled;
-  if (walk_start) (void)hipEventDestroy(walk_start);
-  if (walk_end) (void)hipEventDestroy(walk_end);
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  for (auto& e : prep_events) (void)hipEventDestroy(e);
-  return rc;
+  if (int rc = w.read_times(nsteps, times, elapsed_ms)) return rc;
+  return w.hand_over();
 }
 
 static bool graph_pairs_match(const tn_net* net, const u64* pairs,
@@ -2860,17 +2797,7 @@ static int contract_graph_replay(tn_net* net, double* elapsed_ms) {
 static int contract_graph_capture(tn_net* net, const u64* pairs,
                                   size_t nsteps) {
   HIP_CHECK(hipSetDevice(net->device));
-  // release the previous final OUTSIDE capture (the release may hipFree,
-  // and hipFree device-syncs — illegal while the stream captures)
-  if (net->has_final && net->final_t.owned) {
-    if (net->final_in_arena)
-      net->arena.release(net->final_t.data);
-    else
-      (void)hipFree(net->final_t.data);
-    net->final_t = DevTensor();
-    net->has_final = false;
-    net->final_in_arena = false;
-  }
+  release_final(net);  // outside the capture; the walk then finds none
   HIP_CHECK(hipStreamSynchronize(net->stream));
   if (hipStreamBeginCapture(net->stream, hipStreamCaptureModeThreadLocal) !=
       hipSuccess) {
@@ -2878,15 +2805,13 @@ static int contract_graph_capture(tn_net* net, const u64* pairs,
     net->graph_state = -1;
     return TN_ERR_HIP;
   }
-  std::vector<void*> deferred;
-  bool spilled = false;
-  int rc = contract_impl(net, pairs, nsteps, nullptr, nullptr, nullptr,
-                         nullptr, /*capture=*/true, &deferred, &spilled);
+  CaptureLog cap;
+  int rc = contract_impl(net, pairs, nsteps, StepTimes(), nullptr, &cap);
   hipGraph_t g = nullptr;
   hipError_t ce = hipStreamEndCapture(net->stream, &g);
-  for (void* p : deferred) (void)hipFree(p);
+  for (void* p : cap.deferred) (void)hipFree(p);
   (void)hipGetLastError();
-  if (rc != TN_OK || ce != hipSuccess || !g || spilled) {
+  if (rc != TN_OK || ce != hipSuccess || !g || cap.spilled) {
     if (g) (void)hipGraphDestroy(g);
     net->graph_state = -1;  // caller falls back to a normal run
     return rc != TN_OK ? rc : TN_ERR_HIP;
@@ -2920,8 +2845,7 @@ extern "C" int tn_net_contract(tn_net* net, const u64* pairs, size_t nsteps,
       return contract_graph_replay(net, elapsed_ms);
     // capture failed (workspace spill etc.) — run normally below
   }
-  int rc = contract_impl(net, pairs, nsteps, nullptr, nullptr, nullptr,
-                         elapsed_ms);
+  int rc = contract_impl(net, pairs, nsteps, StepTimes(), elapsed_ms);
   if (rc == TN_OK && net->graph_state >= 0 && net->arena.base) {
     net->graph_pairs.assign(pairs, pairs + 2 * nsteps);
     net->graph_state = 1;  // arm capture for the next identical call
@@ -2936,8 +2860,8 @@ extern "C" int tn_net_contract_profiled(tn_net* net, const u64* pairs,
   if (!net) FAILV(TN_ERR_INVALID, "null net");
   if (net->graph_state == 2 && !graph_pairs_match(net, pairs, nsteps))
     net->invalidate_graph();  // different path moves the final block
-  int rc =
-      contract_impl(net, pairs, nsteps, step_ms, gemm_ms, kind, elapsed_ms);
+  int rc = contract_impl(net, pairs, nsteps, StepTimes{step_ms, gemm_ms, kind},
+                         elapsed_ms);
   if (rc == TN_OK && net->graph_state == 0 && net->arena.base) {
     net->graph_pairs.assign(pairs, pairs + 2 * nsteps);
     net->graph_state = 1;  // a profiled pass also arms graph capture
