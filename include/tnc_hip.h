@@ -165,6 +165,26 @@ int tn_plan_layouts(int dtype, const uint64_t* leaf_labels,
                     size_t nleaves, const uint64_t* pairs, size_t nsteps,
                     int32_t* scatter_out, uint64_t* inline_pack_bytes);
 
+/* The slice plan of tn_net_contract_sliced: leaves and path as for
+ * tn_plan_layouts, plus the labels to fix. *nassign gets the number of
+ * assignments (the product of the labels' dims); assignment index t decodes
+ * with the first label most significant, the order of a nested loop with the
+ * first label outermost. reduced_nd[nleaves] gets each leaf's rank with the
+ * slice labels removed, strides[nleaves * nlabels] (row-major) the element
+ * stride of each slice label in each stored leaf, 0 where the leaf does not
+ * carry it: the flat offset of assignment t in a leaf is the sum over labels
+ * of digit * stride. Any output may be NULL. Returns TN_ERR_INVALID, with the
+ * text in tn_last_error, when a label is in no leaf, is listed twice, is
+ * carried by a number of leaves other than two or is a leg of the final
+ * tensor, when the assignment count overflows 64 bits, and for a path
+ * tn_plan_layouts refuses. Needs no GPU. */
+int tn_plan_slices(int dtype, const uint64_t* leaf_labels,
+                   const uint64_t* leaf_dims, const uint64_t* leaf_nd,
+                   size_t nleaves, const uint64_t* pairs, size_t nsteps,
+                   const uint64_t* slice_labels, size_t nlabels,
+                   uint64_t* nassign, uint64_t* reduced_nd,
+                   uint64_t* strides);
+
 /* ------------ network executor (contract_tensor_network) ------------- */
 
 typedef struct tn_net tn_net;
@@ -205,6 +225,23 @@ int tn_net_contract(tn_net* net, const uint64_t* pairs, size_t nsteps,
 int tn_net_contract_profiled(tn_net* net, const uint64_t* pairs, size_t nsteps,
                              double* step_ms, double* gemm_ms, int32_t* kind,
                              double* elapsed_ms);
+
+/* Contract the network as the sum, over the listed assignments of the slice
+ * labels, of the network with those labels fixed. Same path for every
+ * assignment. which[nwhich] are assignment indices (first label most
+ * significant); the result (tn_net_result_*) is the sum in that order.
+ * nlabels == 0 with which = {0} is the plain contraction.
+ * The leaves stay as uploaded: each assignment gathers the leaves that carry
+ * a slice label into per-net shadow buffers on the device, walks the path as
+ * a net holding the reduced leaves would, and adds its final tensor to an
+ * accumulator, all on the net's stream without a host wait in between.
+ * elapsed_ms (optional) gets the device time of all assignments. Returns
+ * TN_ERR_INVALID, with nothing launched, for a slice plan tn_plan_slices
+ * refuses, an index at or beyond the assignment count, and nwhich == 0. */
+int tn_net_contract_sliced(tn_net* net, const uint64_t* pairs, size_t nsteps,
+                           const uint64_t* slice_labels, size_t nlabels,
+                           const uint64_t* which, size_t nwhich,
+                           double* elapsed_ms);
 
 /* Synchronous device-to-device copy on the current device (for exchanging
  * buffers with an external allocator, e.g. RCCL-communicated tensors). */

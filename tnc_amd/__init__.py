@@ -35,4 +35,5 @@ from .repartition import (
     balance_partitions,
     compute_solution,
 )
-from .slicing import find_slice_edges, slice_network
+from .slicing import (contract_sliced_device, find_slice_edges,
+                      slice_network)

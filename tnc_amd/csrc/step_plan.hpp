@@ -7,7 +7,10 @@
 // compiler and runs without a GPU. The executor (einsum_dev_impl), the walk
 // plan of a whole path (plan_layouts, below: stored orders and look-ahead
 // packs) and the Python arena model (through tn_plan_step) all read this
-// plan; none re-derives it. Only what depends on
+// plan; none re-derives it. plan_slices (at the end) is the same for edge
+// slicing: reduced leaves, per-leaf offsets and the walk plan of one slice,
+// read by tn_net_contract_sliced and through tn_plan_slices. Only what
+// depends on
 // an allocation failing at run time stays in the executor: split-K falling
 // back to 1, the pipeline to the serial pack, out-of-memory to the gather
 // route.
@@ -802,6 +805,125 @@ inline void plan_layouts(bool c128, const std::vector<LayoutTensor>& leaves,
     stored[i] = chosen;
   }
   lp->valid = true;
+}
+
+// ---- slice plan -----------------------------------------------------------
+// Edge slicing contracts the network as a sum over the index values of some
+// shared labels. Fixing a label's value removes that leg from the two leaves
+// carrying it; the same path then contracts the reduced leaves. Everything
+// that follows from (leaves, path, slice labels) is decided here, once:
+//   - the reduced leaf set (sliced labels removed, order of the rest kept),
+//     and the walk plan of the path over it: plan_layouts, unchanged, so the
+//     sliced walk stores, packs and routes exactly as a fresh net holding
+//     the reduced leaves would;
+//   - per leaf and slice label, the element stride of that label in the
+//     stored (full) leaf, 0 where the leaf does not carry it;
+//   - the radices (dims of the slice labels) and the assignment count.
+// Assignment t decodes with the FIRST label most significant (the order of
+// itertools.product): digit x = (t / weight[x]) % radix[x], weight[x] the
+// product of the radices after x. The source offset of a sliced leaf under
+// assignment t is the sum over labels of digit * stride.
+
+struct SlicePlan {
+  bool valid = false;  // false: refused, `err` says why
+  std::string err;
+  std::vector<u64> labels, radices, weights;  // per slice label
+  u64 count = 1;                              // number of assignments
+  std::vector<LayoutTensor> reduced;          // per leaf
+  std::vector<u64> strides;                   // nleaves x nslice, row-major
+  std::vector<char> sliced;                   // per leaf: carries a label
+  LayoutPlan layout;                          // plan_layouts over `reduced`
+};
+
+inline void plan_slices(bool c128, const std::vector<LayoutTensor>& leaves,
+                        const u64* pairs, size_t nsteps,
+                        const u64* slice_labels, size_t nlabels,
+                        SlicePlan* sp) {
+  *sp = SlicePlan();
+  const size_t n = leaves.size();
+  char buf[160];
+  auto refuse = [&](const char* fmt, u64 a, u64 b = 0) {
+    snprintf(buf, sizeof buf, fmt, (unsigned long long)a,
+             (unsigned long long)b);
+    sp->err = buf;
+  };
+  // the legs the path leaves open: a legs-only walk of the path
+  std::vector<std::vector<u64>> legs(n);
+  std::vector<char> alive(n, 1);
+  for (size_t x = 0; x < n; ++x) legs[x] = leaves[x].labels;
+  for (size_t s = 0; s < nsteps; ++s) {
+    const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
+    if (i >= n || j >= n || i == j || !alive[i] || !alive[j]) {
+      sp->err = "invalid contraction path step";
+      return;
+    }
+    std::vector<u64> out;
+    for (u64 l : legs[i])
+      if (std::find(legs[j].begin(), legs[j].end(), l) == legs[j].end())
+        out.push_back(l);
+    for (u64 l : legs[j])
+      if (std::find(legs[i].begin(), legs[i].end(), l) == legs[i].end())
+        out.push_back(l);
+    legs[i].swap(out);
+    legs[j].clear();
+    alive[j] = 0;
+  }
+  sp->labels.assign(slice_labels, slice_labels + nlabels);
+  sp->radices.assign(nlabels, 0);
+  sp->strides.assign(n * nlabels, 0);
+  sp->sliced.assign(n, 0);
+  for (size_t x = 0; x < nlabels; ++x) {
+    const u64 lab = slice_labels[x];
+    for (size_t y = 0; y < x; ++y)
+      if (slice_labels[y] == lab)
+        return refuse("slice label %llu is listed twice", lab);
+    u64 carriers = 0;
+    for (size_t t = 0; t < n; ++t) {
+      const LayoutTensor& lt = leaves[t];
+      u64 stride = 1;
+      for (size_t a = lt.labels.size(); a-- > 0;) {
+        if (lt.labels[a] == lab) {
+          if (sp->strides[t * nlabels + x])
+            return refuse("slice label %llu is repeated within leaf %llu", lab,
+                          (u64)t);
+          ++carriers;
+          sp->radices[x] = lt.dims[a];
+          sp->strides[t * nlabels + x] = stride;
+          sp->sliced[t] = 1;
+        }
+        stride *= lt.dims[a];
+      }
+    }
+    if (carriers == 0) return refuse("slice label %llu is in no leaf", lab);
+    for (size_t t = 0; t < n; ++t)
+      if (alive[t] && std::find(legs[t].begin(), legs[t].end(), lab) !=
+                          legs[t].end())
+        return refuse("slice label %llu is a leg of the final tensor", lab);
+    if (carriers != 2)
+      return refuse("slice label %llu is carried by %llu leaves, not two", lab,
+                    carriers);
+  }
+  sp->weights.assign(nlabels, 1);
+  for (size_t x = nlabels; x-- > 0;) {
+    sp->weights[x] = sp->count;
+    if (__builtin_mul_overflow(sp->count, sp->radices[x], &sp->count))
+      return refuse("assignment count of %llu slice labels overflows 64 bits",
+                    (u64)nlabels);
+  }
+  sp->reduced.resize(n);
+  for (size_t t = 0; t < n; ++t)
+    for (size_t a = 0; a < leaves[t].labels.size(); ++a)
+      if (std::find(sp->labels.begin(), sp->labels.end(),
+                    leaves[t].labels[a]) == sp->labels.end()) {
+        sp->reduced[t].labels.push_back(leaves[t].labels[a]);
+        sp->reduced[t].dims.push_back(leaves[t].dims[a]);
+      }
+  plan_layouts(c128, sp->reduced, pairs, nsteps, &sp->layout);
+  if (!sp->layout.valid) {
+    sp->err = sp->layout.err;
+    return;
+  }
+  sp->valid = true;
 }
 
 #endif  // TNC_STEP_PLAN_HPP

@@ -2203,6 +2203,31 @@ extern "C" int tn_plan_layouts(int dtype, const u64* leaf_labels,
   return TN_OK;
 }
 
+extern "C" int tn_plan_slices(int dtype, const u64* leaf_labels,
+                              const u64* leaf_dims, const u64* leaf_nd,
+                              size_t nleaves, const u64* pairs, size_t nsteps,
+                              const u64* slice_labels, size_t nlabels,
+                              u64* nassign, u64* reduced_nd, u64* strides) {
+  if ((dtype != 0 && dtype != 1) || (nleaves && !leaf_nd) ||
+      (nsteps && !pairs) || (nlabels && !slice_labels))
+    FAILV(TN_ERR_INVALID, "unknown dtype or null leaves/pairs/slice labels");
+  std::vector<LayoutTensor> lt(nleaves);
+  size_t at = 0;
+  for (size_t x = 0; x < nleaves; ++x) {
+    lt[x].labels.assign(leaf_labels + at, leaf_labels + at + leaf_nd[x]);
+    lt[x].dims.assign(leaf_dims + at, leaf_dims + at + leaf_nd[x]);
+    at += leaf_nd[x];
+  }
+  SlicePlan sp;
+  plan_slices(dtype == 0, lt, pairs, nsteps, slice_labels, nlabels, &sp);
+  if (!sp.valid) FAILV(TN_ERR_INVALID, "%s", sp.err.c_str());
+  if (nassign) *nassign = sp.count;
+  for (size_t x = 0; reduced_nd && x < nleaves; ++x)
+    reduced_nd[x] = sp.reduced[x].labels.size();
+  if (strides) std::copy(sp.strides.begin(), sp.strides.end(), strides);
+  return TN_OK;
+}
+
 static u64 span_elems(const u64* shape, const i64* strides, size_t nd) {
   // max linear offset + 1, assuming nonnegative strides
   u64 span = 1;
@@ -2283,6 +2308,104 @@ extern "C" int tn_einsum_c64(const u64* out_labels, const u64* out_shape,
                                    b_ndim, out_data);
 }
 
+// --- edge slicing (tn_net_contract_sliced) ---------------------------------
+// Both kernels read the assignment from a control record in device memory,
+// not from a launch argument: a captured graph of gather -> walk ->
+// accumulate is then the same for every assignment.
+
+struct SliceCtl {
+  u64 t;      // assignment index, first slice label most significant
+  u64 first;  // nonzero: this assignment starts the sum
+};
+
+// One sliced leaf: dst[p] = src[base(t) + gather(p)], p over the remaining
+// dims (row-major). pstride/dim are shift/mask when pow2 is set, suffix
+// product/dim otherwise (the split of k_permute_ct).
+struct SliceDesc {
+  const void* src;
+  void* dst;
+  u64 elems;
+  int nd, pow2, nsl, pad;
+  u64 pstride[TN_MAXR], dim[TN_MAXR], sstride[TN_MAXR];
+  // the leaf's slice labels: digit = (t / weight) % radix, times stride
+  u64 sl_stride[TN_MAXR], sl_weight[TN_MAXR], sl_radix[TN_MAXR];
+};
+
+// blockIdx.y = sliced leaf, grid-stride over its elements in x
+template <typename CT>
+__global__ void k_slice_gather(const SliceDesc* __restrict__ descs,
+                               const SliceCtl* __restrict__ ctl) {
+  const SliceDesc& d = descs[blockIdx.y];
+  const u64 t = ctl->t;
+  u64 base = 0;
+  for (int x = 0; x < d.nsl; ++x)
+    base += ((t / d.sl_weight[x]) % d.sl_radix[x]) * d.sl_stride[x];
+  const CT* __restrict__ src = (const CT*)d.src + base;
+  CT* __restrict__ dst = (CT*)d.dst;
+  const int nd = d.nd;
+  const bool p2 = d.pow2 != 0;
+  for (u64 p = blockIdx.x * (u64)blockDim.x + threadIdx.x; p < d.elems;
+       p += gridDim.x * (u64)blockDim.x) {
+    u64 off = 0;
+    for (int i = 0; i < nd; ++i) {
+      const u64 c = p2 ? ((p >> d.pstride[i]) & d.dim[i])
+                       : ((p / d.pstride[i]) % d.dim[i]);
+      off += c * d.sstride[i];
+    }
+    dst[p] = src[off];
+  }
+}
+
+// acc[p] = first ? part[p] : acc[p] + part[p], 16 bytes per lane: one c128
+// element, or two c64 elements with a scalar tail for an odd count. Plain
+// adds in assignment order, so the sum is the IEEE sequence of a host loop
+// `total += part`.
+__global__ void k_slice_accumulate(double2* __restrict__ acc,
+                                   const double2* __restrict__ part, u64 n,
+                                   const SliceCtl* __restrict__ ctl) {
+  const bool first = ctl->first != 0;
+  for (u64 p = blockIdx.x * (u64)blockDim.x + threadIdx.x; p < n;
+       p += gridDim.x * (u64)blockDim.x) {
+    double2 v = part[p];
+    if (!first) {
+      const double2 a = acc[p];
+      v.x = a.x + v.x;
+      v.y = a.y + v.y;
+    }
+    acc[p] = v;
+  }
+}
+
+__global__ void k_slice_accumulate(float2* __restrict__ acc,
+                                   const float2* __restrict__ part, u64 n,
+                                   const SliceCtl* __restrict__ ctl) {
+  const bool first = ctl->first != 0;
+  const u64 npair = n / 2;
+  float4* __restrict__ acc4 = (float4*)acc;
+  const float4* __restrict__ part4 = (const float4*)part;
+  for (u64 p = blockIdx.x * (u64)blockDim.x + threadIdx.x; p < npair;
+       p += gridDim.x * (u64)blockDim.x) {
+    float4 v = part4[p];
+    if (!first) {
+      const float4 a = acc4[p];
+      v.x = a.x + v.x;
+      v.y = a.y + v.y;
+      v.z = a.z + v.z;
+      v.w = a.w + v.w;
+    }
+    acc4[p] = v;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    float2 v = part[n - 1];
+    if (!first) {
+      const float2 a = acc[n - 1];
+      v.x = a.x + v.x;
+      v.y = a.y + v.y;
+    }
+    acc[n - 1] = v;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // network executor (contract_tensor_network replacement)
 // ---------------------------------------------------------------------------
@@ -2293,6 +2416,35 @@ struct DevTensor : LayoutTensor {
   u64 elems = 1;
   bool owned = false;     // intermediate owned by the walk (freed on consume)
   bool external = false;  // caller-owned device buffer (never freed by us)
+};
+
+// What tn_net_contract_sliced keeps per (path, slice labels): the slice plan
+// with its reduced walk plan, the shadow leaves (one slab, rewritten by
+// k_slice_gather for every assignment), the descriptor table and the control
+// record on the device, and the captured graph of one assignment.
+struct SliceState {
+  std::vector<u64> pairs, labels;  // the key
+  SlicePlan plan;
+  std::vector<DevTensor> leaves;  // shadows where sliced, originals otherwise
+  void* slab = nullptr;           // the shadow leaves' storage
+  bool slab_in_arena = false;
+  void* descs = nullptr;  // SliceDesc[ndesc]
+  unsigned ndesc = 0;
+  u64 max_elems = 0;      // largest shadow leaf
+  void* ctl = nullptr;    // SliceCtl the kernels read
+  void* table = nullptr;  // SliceCtl[table_cap], one per listed assignment
+  size_t table_cap = 0;
+  // graph of gather -> walk -> accumulate; states as tn_net::graph_state
+  hipGraphExec_t graph_exec = nullptr;
+  int graph_state = 0;
+  void* graph_acc = nullptr;  // the accumulator address the graph bakes
+
+  void drop_graph() {
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    graph_exec = nullptr;
+    graph_acc = nullptr;
+    if (graph_state > 0) graph_state = 0;
+  }
 };
 
 struct tn_net {
@@ -2322,12 +2474,40 @@ struct tn_net {
   int graph_state = 0;  // 0 = no normal run yet, 1 = ready to capture,
                         // 2 = captured, -1 = disabled (spill/failure)
 
-  void invalidate_graph() {
+  // edge slicing: the state of the last (path, slice labels) contracted. Its
+  // graph and the one above never coexist: a sliced call drops the unsliced
+  // graph and an unsliced call the sliced one, since each walk's arena
+  // blocks are free for the other to take.
+  SliceState* slices = nullptr;
+
+  void drop_graph() {
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     graph_exec = nullptr;
     graph_pairs.clear();
     if (graph_state > 0) graph_state = 0;
+  }
+
+  void drop_slices() {
+    if (!slices) return;
+    (void)hipStreamSynchronize(stream);
+    slices->drop_graph();
+    if (slices->slab) {
+      if (slices->slab_in_arena)
+        arena.release(slices->slab);
+      else
+        (void)hipFree(slices->slab);
+    }
+    if (slices->descs) (void)hipFree(slices->descs);
+    if (slices->ctl) (void)hipFree(slices->ctl);
+    if (slices->table) (void)hipFree(slices->table);
+    delete slices;
+    slices = nullptr;
+  }
+
+  void invalidate_graph() {
+    drop_graph();
     layout_known = false;  // same triggers: the network or the arena changed
+    drop_slices();
   }
 };
 
@@ -2498,15 +2678,21 @@ struct Walk {
   std::vector<hipEvent_t> prof_ev;  // per step: start, end, gemm start, end
   hipEvent_t walk_start = nullptr, walk_end = nullptr;
   const bool overlap;
+  // false: one assignment of a sliced run, which neither synchronises nor
+  // times itself (tn_net_contract_sliced times the whole call)
+  const bool timed;
   bool done = false;  // the final tensor was handed over
 
-  Walk(tn_net* n, CaptureLog* c)
+  // `leaves`: the net's own, or a sliced run's shadow leaves in their place
+  Walk(tn_net* n, CaptureLog* c, const std::vector<DevTensor>& leaves,
+       bool timed_ = true)
       : net(n), cap(c),
         ws{n->arena.base ? &n->arena : nullptr, n->stream, c != nullptr, false,
            c ? &c->deferred : nullptr},
-        slots(n->leaves), alive(n->leaves.size(), 1),
+        slots(leaves), alive(leaves.size(), 1),
         overlap(!env_switch(ENV_NO_PREPACK) && n->stream2 &&
-                n->arena.base != nullptr) {
+                n->arena.base != nullptr),
+        timed(timed_) {
     ws.stream2 = n->stream2;
     ws.events = &events;
     for (auto& s : slots) s.owned = false;  // shallow copies
@@ -2540,7 +2726,7 @@ struct Walk {
       prof_ev.push_back(new_event());
       if (!prof_ev.back()) FAILV(TN_ERR_HIP, "hipEventCreate failed");
     }
-    if (cap) return TN_OK;
+    if (cap || !timed) return TN_OK;
     HIP_CHECK(hipStreamSynchronize(net->stream));
     walk_start = new_event();
     walk_end = new_event();
@@ -2685,7 +2871,7 @@ struct Walk {
   // close the timed span and read the timings back
   int read_times(size_t nsteps, const StepTimes& times, double* elapsed_ms) {
     float ms = 0.f;
-    if (!cap) {
+    if (!cap && timed) {
       HIP_CHECK(hipEventRecord(walk_end, net->stream));
       HIP_CHECK(hipStreamSynchronize(net->stream));
       HIP_CHECK(hipEventElapsedTime(&ms, walk_start, walk_end));
@@ -2732,20 +2918,32 @@ struct Walk {
     done = true;
     return TN_OK;
   }
+
+  // a sliced run's ending: the one tensor left is this assignment's part of
+  // the sum. Add it to acc (or start acc with it) and give its block back;
+  // the next user of the block is ordered behind the kernel on the stream.
+  int fold_into(void* acc, const void* ctl) {
+    size_t x = 0;
+    while (!alive[x]) ++x;
+    DevTensor& f = slots[x];
+    with_dtype(net->dtype, [&](auto* t) {
+      typedef std::remove_pointer_t<decltype(t)> CT;
+      const u64 lanes = sizeof(CT) == 16 ? f.elems : (f.elems + 1) / 2;
+      k_slice_accumulate<<<grid_for(lanes), 256, 0, net->stream>>>(
+          (CT*)acc, (const CT*)f.data, f.elems, (const SliceCtl*)ctl);
+      return 0;
+    });
+    HIP_CHECK(hipGetLastError());
+    if (f.owned) ws_free(ws, f.data);
+    f.owned = false;
+    done = true;
+    return TN_OK;
+  }
 };
 
-static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
-                         const StepTimes& times, double* elapsed_ms,
-                         CaptureLog* cap = nullptr) {
-  if (!net) FAILV(TN_ERR_INVALID, "null net");
-  HIP_CHECK(hipSetDevice(net->device));
-  release_final(net);
-  const LayoutPlan& plan = walk_plan(net, pairs, nsteps);
-  if (!plan.valid) FAILV(TN_ERR_INVALID, "%s", plan.err.c_str());
-  if (net->leaves.size() != nsteps + 1)
-    FAILV(TN_ERR_INVALID, "path did not fully contract the network");
-  Walk w(net, cap);
-  if (int rc = w.begin(nsteps, times.step_ms != nullptr)) return rc;
+// the step loop of a walk: join, allocate, look ahead, dispatch, retire
+static int walk_steps(Walk& w, const LayoutPlan& plan, const u64* pairs,
+                      size_t nsteps, const StepTimes& times) {
   for (size_t s = 0; s < nsteps; ++s) {
     const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
     int rc = w.join_prepack();
@@ -2757,6 +2955,22 @@ static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
     if (rc != TN_OK) return rc;
     w.retire(i, j);
   }
+  return TN_OK;
+}
+
+static int contract_impl(tn_net* net, const u64* pairs, size_t nsteps,
+                         const StepTimes& times, double* elapsed_ms,
+                         CaptureLog* cap = nullptr) {
+  if (!net) FAILV(TN_ERR_INVALID, "null net");
+  HIP_CHECK(hipSetDevice(net->device));
+  release_final(net);
+  const LayoutPlan& plan = walk_plan(net, pairs, nsteps);
+  if (!plan.valid) FAILV(TN_ERR_INVALID, "%s", plan.err.c_str());
+  if (net->leaves.size() != nsteps + 1)
+    FAILV(TN_ERR_INVALID, "path did not fully contract the network");
+  Walk w(net, cap, net->leaves);
+  if (int rc = w.begin(nsteps, times.step_ms != nullptr)) return rc;
+  if (int rc = walk_steps(w, plan, pairs, nsteps, times)) return rc;
   if (int rc = w.read_times(nsteps, times, elapsed_ms)) return rc;
   return w.hand_over();
 }
@@ -2832,6 +3046,7 @@ static int contract_graph_capture(tn_net* net, const u64* pairs,
 extern "C" int tn_net_contract(tn_net* net, const u64* pairs, size_t nsteps,
                                double* elapsed_ms) {
   if (!net) FAILV(TN_ERR_INVALID, "null net");
+  if (net->slices) net->slices->drop_graph();  // its blocks are ours to take
   if (net->graph_state == 2) {
     // a failed walk since capture clears final_t, whose address the replay
     // relies on — in that case re-run (and re-capture) normally
@@ -2858,6 +3073,7 @@ extern "C" int tn_net_contract_profiled(tn_net* net, const u64* pairs,
                                         double* gemm_ms, int32_t* kind,
                                         double* elapsed_ms) {
   if (!net) FAILV(TN_ERR_INVALID, "null net");
+  if (net->slices) net->slices->drop_graph();
   if (net->graph_state == 2 && !graph_pairs_match(net, pairs, nsteps))
     net->invalidate_graph();  // different path moves the final block
   int rc = contract_impl(net, pairs, nsteps, StepTimes{step_ms, gemm_ms, kind},
@@ -2867,6 +3083,280 @@ extern "C" int tn_net_contract_profiled(tn_net* net, const u64* pairs,
     net->graph_state = 1;  // a profiled pass also arms graph capture
   }
   return rc;
+}
+
+// ---- sliced contraction ---------------------------------------------------
+// The sum over slice assignments of the network with the slice labels fixed:
+// per assignment one gather of the sliced leaves into their shadows, the
+// same walk over the reduced plan, and one accumulate of its final tensor.
+// The assignment reaches the kernels through the control record, which a
+// 16-byte device-to-device copy sets between walks, so the host never waits
+// between assignments and one captured graph serves them all.
+
+// shadow leaves, descriptor table and control record of a fresh slice plan
+static int build_slice_buffers(tn_net* net, SliceState& S) {
+  const SlicePlan& sp = S.plan;
+  const size_t n = net->leaves.size(), nl = sp.labels.size();
+  S.leaves.assign(net->leaves.begin(), net->leaves.end());
+  std::vector<u64> off(n, 0);
+  u64 total = 0;
+  for (size_t x = 0; x < n; ++x) {
+    S.leaves[x].owned = false;
+    if (!sp.sliced[x]) continue;
+    u64 elems = 1;
+    for (u64 d : sp.reduced[x].dims) elems *= d;
+    off[x] = total;
+    total += (elems * net->esize + 255) & ~(u64)255;
+    S.max_elems = std::max(S.max_elems, elems);
+    ++S.ndesc;
+  }
+  if (S.ndesc > 65535) FAILV(TN_ERR_INVALID, "more than 65535 sliced leaves");
+  if (total) {
+    S.slab = net->arena.alloc(total);
+    S.slab_in_arena = S.slab != nullptr;
+    if (!S.slab && hipMalloc(&S.slab, total) != hipSuccess) {
+      (void)hipGetLastError();
+      S.slab = nullptr;
+      FAILV(TN_ERR_OOM, "device allocation failed for the shadow leaves");
+    }
+  }
+  std::vector<SliceDesc> descs;
+  for (size_t x = 0; x < n; ++x) {
+    if (!sp.sliced[x]) continue;
+    const DevTensor& full = net->leaves[x];
+    DevTensor& sh = S.leaves[x];
+    static_cast<LayoutTensor&>(sh) = sp.reduced[x];
+    sh.elems = 1;
+    for (u64 d : sh.dims) sh.elems *= d;
+    sh.data = (char*)S.slab + off[x];
+    sh.external = true;  // the slab is the state's, never a walk's
+    SliceDesc d{};
+    d.src = full.data;
+    d.dst = sh.data;
+    d.elems = sh.elems;
+    // remaining axes of the stored leaf, with their source strides
+    std::vector<AxisInfo> ax;
+    u64 stride = 1;
+    for (size_t a = full.labels.size(); a-- > 0;) {
+      if (std::find(sp.labels.begin(), sp.labels.end(), full.labels[a]) ==
+          sp.labels.end())
+        ax.insert(ax.begin(), AxisInfo{full.dims[a], (i64)stride, 0});
+      stride *= full.dims[a];
+    }
+    d.nd = (int)ax.size();
+    d.pow2 = axes_pow2(ax) ? 1 : 0;
+    u64 pstride = 1;
+    for (int i = d.nd - 1; i >= 0; --i) {
+      d.pstride[i] = d.pow2 ? (u64)log2_u64(pstride) : pstride;
+      d.dim[i] = d.pow2 ? ax[i].dim - 1 : ax[i].dim;
+      d.sstride[i] = (u64)ax[i].sa;
+      pstride *= ax[i].dim;
+    }
+    for (size_t l = 0; l < nl; ++l) {
+      if (!sp.strides[x * nl + l]) continue;
+      d.sl_stride[d.nsl] = sp.strides[x * nl + l];
+      d.sl_weight[d.nsl] = sp.weights[l];
+      d.sl_radix[d.nsl] = sp.radices[l];
+      ++d.nsl;
+    }
+    descs.push_back(d);
+  }
+  if (!descs.empty()) {
+    HIP_CHECK(hipMalloc(&S.descs, descs.size() * sizeof(SliceDesc)));
+    HIP_CHECK(hipMemcpy(S.descs, descs.data(),
+                        descs.size() * sizeof(SliceDesc),
+                        hipMemcpyHostToDevice));
+  }
+  HIP_CHECK(hipMalloc(&S.ctl, sizeof(SliceCtl)));
+  return TN_OK;
+}
+
+// the net's slice state for this (path, slice labels), built when the key
+// differs. A refused plan leaves the net as it was.
+static int slice_state(tn_net* net, const u64* pairs, size_t nsteps,
+                       const u64* labels, size_t nlabels, SliceState** out) {
+  SliceState* S = net->slices;
+  if (S && S->pairs.size() == 2 * nsteps && S->labels.size() == nlabels &&
+      std::equal(S->pairs.begin(), S->pairs.end(), pairs) &&
+      std::equal(S->labels.begin(), S->labels.end(), labels)) {
+    *out = S;
+    return TN_OK;
+  }
+  S = new SliceState();
+  const std::vector<LayoutTensor> lt(net->leaves.begin(), net->leaves.end());
+  plan_slices(net->dtype == 0, lt, pairs, nsteps, labels, nlabels, &S->plan);
+  if (!S->plan.valid) {
+    g_last_error = S->plan.err;
+    delete S;
+    return TN_ERR_INVALID;
+  }
+  net->drop_slices();
+  S->pairs.assign(pairs, pairs + 2 * nsteps);
+  S->labels.assign(labels, labels + nlabels);
+  net->slices = S;
+  if (int rc = build_slice_buffers(net, *S)) {
+    const std::string why = g_last_error;
+    net->drop_slices();
+    g_last_error = why;
+    return rc;
+  }
+  *out = S;
+  return TN_OK;
+}
+
+// one assignment: gather -> walk -> accumulate, on net->stream
+static int sliced_unit(tn_net* net, SliceState& S, void* acc,
+                       CaptureLog* cap) {
+  const size_t nsteps = S.pairs.size() / 2;
+  if (S.ndesc) {
+    const dim3 grid((unsigned)grid_for(S.max_elems), S.ndesc);
+    with_dtype(net->dtype, [&](auto* t) {
+      typedef std::remove_pointer_t<decltype(t)> CT;
+      k_slice_gather<CT><<<grid, 256, 0, net->stream>>>(
+          (const SliceDesc*)S.descs, (const SliceCtl*)S.ctl);
+      return 0;
+    });
+    HIP_CHECK(hipGetLastError());
+  }
+  Walk w(net, cap, S.leaves, false);
+  if (int rc = w.begin(nsteps, false)) return rc;
+  if (int rc = walk_steps(w, S.plan.layout, S.pairs.data(), nsteps,
+                          StepTimes()))
+    return rc;
+  return w.fold_into(acc, S.ctl);
+}
+
+// capture one assignment's unit; on any failure the state is -1 and the
+// caller runs the assignment normally (nothing of the capture has executed)
+static int sliced_capture(tn_net* net, SliceState& S, void* acc) {
+  // the one host wait besides the call's last: when the graph is (re)built
+  HIP_CHECK(hipStreamSynchronize(net->stream));
+  if (hipStreamBeginCapture(net->stream, hipStreamCaptureModeThreadLocal) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    S.graph_state = -1;
+    return TN_ERR_HIP;
+  }
+  CaptureLog cap;
+  int rc = sliced_unit(net, S, acc, &cap);
+  hipGraph_t g = nullptr;
+  hipError_t ce = hipStreamEndCapture(net->stream, &g);
+  for (void* p : cap.deferred) (void)hipFree(p);
+  (void)hipGetLastError();
+  hipGraphExec_t exec = nullptr;
+  if (rc == TN_OK && (ce != hipSuccess || !g || cap.spilled)) rc = TN_ERR_HIP;
+  if (rc == TN_OK &&
+      hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    rc = TN_ERR_HIP;
+  }
+  if (g) (void)hipGraphDestroy(g);
+  if (rc != TN_OK) {
+    S.graph_state = -1;
+    return rc;
+  }
+  S.graph_exec = exec;
+  S.graph_state = 2;
+  S.graph_acc = acc;
+  return TN_OK;
+}
+
+// all listed assignments, then the one wait that closes the call. The rules
+// of tn_net_contract: first run normal, second captured, later ones replayed.
+static int sliced_loop(tn_net* net, SliceState& S, size_t nwhich, void* acc,
+                       hipEvent_t e0, hipEvent_t e1, double* elapsed_ms) {
+  HIP_CHECK(hipEventRecord(e0, net->stream));
+  for (size_t k = 0; k < nwhich; ++k) {
+    HIP_CHECK(hipMemcpyAsync(S.ctl, (const SliceCtl*)S.table + k,
+                             sizeof(SliceCtl), hipMemcpyDeviceToDevice,
+                             net->stream));
+    // the graph writes to the accumulator it was captured with
+    if (S.graph_state == 2 && S.graph_acc != acc) S.drop_graph();
+    if (S.graph_state == 1 && net->arena.base)
+      (void)sliced_capture(net, S, acc);
+    if (S.graph_state == 2) {
+      if (hipGraphLaunch(S.graph_exec, net->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        S.drop_graph();
+        S.graph_state = -1;
+        FAILV(TN_ERR_HIP, "hipGraphLaunch failed");
+      }
+      continue;
+    }
+    if (int rc = sliced_unit(net, S, acc, nullptr)) return rc;
+    if (S.graph_state == 0 && net->arena.base) S.graph_state = 1;
+  }
+  HIP_CHECK(hipEventRecord(e1, net->stream));
+  HIP_CHECK(hipStreamSynchronize(net->stream));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  if (elapsed_ms) *elapsed_ms = (double)ms;
+  return TN_OK;
+}
+
+extern "C" int tn_net_contract_sliced(tn_net* net, const u64* pairs,
+                                      size_t nsteps, const u64* slice_labels,
+                                      size_t nlabels, const u64* which,
+                                      size_t nwhich, double* elapsed_ms) {
+  if (!net) FAILV(TN_ERR_INVALID, "null net");
+  if (!which || nwhich == 0)
+    FAILV(TN_ERR_INVALID, "no slice assignment listed");
+  if ((nsteps && !pairs) || (nlabels && !slice_labels))
+    FAILV(TN_ERR_INVALID, "null pairs or slice labels");
+  if (net->leaves.size() != nsteps + 1)
+    FAILV(TN_ERR_INVALID, "path did not fully contract the network");
+  HIP_CHECK(hipSetDevice(net->device));
+  SliceState* S = nullptr;
+  if (int rc = slice_state(net, pairs, nsteps, slice_labels, nlabels, &S))
+    return rc;
+  for (size_t k = 0; k < nwhich; ++k)
+    if (which[k] >= S->plan.count)
+      FAILV(TN_ERR_INVALID,
+            "slice assignment %llu out of range (%llu assignments)",
+            (unsigned long long)which[k], (unsigned long long)S->plan.count);
+  net->drop_graph();  // the unsliced graph's blocks are this walk's to take
+  release_final(net);
+
+  // per-call control table: entry k sets up the k-th listed assignment
+  if (S->table_cap < nwhich) {
+    if (S->table) (void)hipFree(S->table);
+    S->table = nullptr;
+    S->table_cap = 0;
+    HIP_CHECK(hipMalloc(&S->table, nwhich * sizeof(SliceCtl)));
+    S->table_cap = nwhich;
+  }
+  std::vector<SliceCtl> table(nwhich);
+  for (size_t k = 0; k < nwhich; ++k) table[k] = {which[k], k == 0 ? 1u : 0u};
+  HIP_CHECK(hipMemcpy(S->table, table.data(), nwhich * sizeof(SliceCtl),
+                      hipMemcpyHostToDevice));
+
+  // the accumulator: the final tensor of the reduced walk, in its order
+  DevTensor f;
+  static_cast<LayoutTensor&>(f) =
+      nsteps ? S->plan.layout.out[nsteps - 1] : S->plan.reduced[0];
+  for (u64 d : f.dims) f.elems *= d;
+  WsCtx ws{net->arena.base ? &net->arena : nullptr, net->stream};
+  if (ws_alloc(ws, &f.data, f.elems * net->esize) != TN_OK)
+    FAILV(TN_ERR_OOM, "device allocation failed for the accumulator");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = TN_OK;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    g_last_error = "hipEventCreate failed";
+    rc = TN_ERR_HIP;
+  }
+  if (rc == TN_OK) rc = sliced_loop(net, *S, nwhich, f.data, e0, e1, elapsed_ms);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (rc != TN_OK) {
+    (void)hipStreamSynchronize(net->stream);
+    ws_free(ws, f.data);
+    return rc;
+  }
+  f.owned = true;
+  net->final_in_arena = net->arena.owns(f.data);
+  net->final_t = std::move(f);
+  net->has_final = true;
+  return TN_OK;
 }
 
 extern "C" int tn_memcpy_dtod(void* dst, const void* src, u64 bytes) {

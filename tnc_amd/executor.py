@@ -59,13 +59,14 @@ def plan_steps(leaves, steps, dtype="c128"):
     return infos
 
 
-def arena_bytes(leaves, steps, infos, esize=16):
+def arena_bytes(leaves, steps, infos, esize=16, exact_dot=False):
     """Peak device-arena demand: live intermediates + this step's output and
     the workspaces its dispatch actually uses, walked over the plan. The
     pack-overlap executor allocates the NEXT step's pack buffers one step
     early (prepack on stream2), so each step's demand includes them.
     Padded 15% for fragmentation + split-K slack (a split buffer that does
-    not fit only costs the step its split)."""
+    not fit only costs the step its split). exact_dot: count a dot step's
+    partials as the plan states them (ws_dot), not by the 32 MiB bound."""
     def pack_ws(p):  # pack buffers, or the pipeline's window buffers
         return p.ws_pack_a + p.ws_pack_b
 
@@ -76,7 +77,10 @@ def arena_bytes(leaves, steps, infos, esize=16):
         p = info.plan
         nxt = pack_ws(infos[s + 1].plan) if s + 1 < len(infos) else 0
         # dot partials: bounded, not exact (<= 2^21 blocks * 16 B)
-        ws = (1 << 25) if p.ws_dot else pack_ws(p) + p.ws_tmp_c + p.ws_slices
+        if p.ws_dot:
+            ws = p.ws_dot if exact_dot else (1 << 25)
+        else:
+            ws = pack_ws(p) + p.ws_tmp_c + p.ws_slices
         demand = sum(live.values()) + out_b + ws + nxt
         peak = max(peak, demand)
         live.pop(info.j, None)
@@ -84,11 +88,50 @@ def arena_bytes(leaves, steps, infos, esize=16):
     return int(peak * 1.15) + (1 << 20)
 
 
+def reduced_leaves(leaves, slice_edges):
+    """The leaves with the sliced legs removed (legs and dims only): what
+    slicing.slice_network produces for any assignment."""
+    cut = set(slice_edges)
+    return [
+        LeafTensor([l for l in t.legs if l not in cut],
+                   [d for l, d in zip(t.legs, t.bond_dims) if l not in cut])
+        for t in leaves
+    ]
+
+
+def sliced_arena_bytes(leaves, steps, slice_edges, dtype="c128"):
+    """Arena demand of a sliced contraction (tn_net_contract_sliced): the
+    walk over the reduced leaves, plus the accumulator (one more final
+    tensor, held for the whole call), plus the shadow leaves (the reduced
+    copy of every leaf that carries a sliced leg, each rounded up to the
+    arena's 256-byte granule). Needs no GPU."""
+    esize = 16 if dtype == "c128" else 8
+    red = reduced_leaves(leaves, slice_edges)
+    infos = plan_steps(red, steps, dtype)
+    cut = set(slice_edges)
+    if infos:
+        acc = infos[-1].m * infos[-1].n * esize
+    else:
+        acc = int(np.prod(red[0].bond_dims, dtype=object)) * esize
+    shadows = sum(
+        (int(np.prod(r.bond_dims, dtype=object)) * esize + 255) // 256 * 256
+        for t, r in zip(leaves, red) if cut & set(t.legs)
+    )
+    # slicing is for networks that do not fit: no 32 MiB allowance for a dot
+    # step's partials where the plan gives their size
+    return (arena_bytes(red, steps, infos, esize, exact_dot=True)
+            + acc + 256 + shadows)
+
+
 class ContractionEngine:
-    """Device-resident executor for one (flattened) network."""
+    """Device-resident executor for one (flattened) network. With
+    `slice_edges` the engine is sized and planned for contract_sliced():
+    infos and total_flops describe one slice, the arena holds one sliced
+    walk, the accumulator and the shadow leaves; the leaves are uploaded
+    whole, once."""
 
     def __init__(self, tn: CompositeTensor, replace_path: ContractionPath,
-                 device=0, dtype="c128"):
+                 device=0, dtype="c128", slice_edges=None):
         if hiplib.device_count() == 0:
             raise RuntimeError("no AMD GPU present — tnc_amd has no CPU fallback")
         assert dtype in ("c128", "c64")
@@ -99,14 +142,28 @@ class ContractionEngine:
         self.leaves = leaves
         self.steps = steps
         self.final = final
-        self.infos = plan_steps(leaves, steps, dtype)
+        self.slice_edges = None if slice_edges is None else list(slice_edges)
+        self.num_slices = 1
+        if self.slice_edges is None:
+            self.infos = plan_steps(leaves, steps, dtype)
+        else:
+            # refuses what the executor would refuse, before anything uploads
+            self.num_slices, _, _ = hiplib.plan_slices(
+                [(t.legs, t.bond_dims) for t in leaves], steps,
+                self.slice_edges, dtype)
+            self.infos = plan_steps(
+                reduced_leaves(leaves, self.slice_edges), steps, dtype)
         self.total_flops = sum(s.flops for s in self.infos)
         L = hiplib.lib()
         hiplib.check(L.tn_set_device(device), "tn_set_device")
         self.net = L.tn_net_create2(device, 0 if dtype == "c128" else 1)
         if not self.net:
             raise RuntimeError(f"tn_net_create failed: {hiplib.last_error()}")
-        reserve = arena_bytes(leaves, steps, self.infos, self.esize)
+        if self.slice_edges is None:
+            reserve = arena_bytes(leaves, steps, self.infos, self.esize)
+        else:
+            reserve = sliced_arena_bytes(leaves, steps, self.slice_edges,
+                                         dtype)
         # launch-bound walks (many tiny steps) only replay as a hipGraph
         # when every workspace comes from the arena — reserve a floor so
         # replay engages (rqc24: ~2.4 ms/contraction unreserved vs
@@ -148,6 +205,29 @@ class ContractionEngine:
                 self.net, self._pairs, len(self.steps), ctypes.byref(ms)
             ),
             "tn_net_contract",
+        )
+        return ms.value
+
+    def contract_sliced(self, which=None) -> float:
+        """The sum over the listed slice assignments (None: all of them, in
+        order) of the network with slice_edges fixed, on the device in one
+        call; result() / result_dev() then give the sum. `which` holds
+        assignment indices, first edge most significant: index t is
+        list(slicing.iter_assignments(tn, slice_edges))[t]. Returns the
+        device ms of all assignments."""
+        if self.slice_edges is None:
+            raise RuntimeError("engine was built without slice_edges")
+        if which is None:
+            which = range(self.num_slices)
+        which = list(which)
+        ms = ctypes.c_double()
+        hiplib.check(
+            hiplib.lib().tn_net_contract_sliced(
+                self.net, self._pairs, len(self.steps),
+                hiplib._u64arr(self.slice_edges), len(self.slice_edges),
+                hiplib._u64arr(which), len(which), ctypes.byref(ms)
+            ),
+            "tn_net_contract_sliced",
         )
         return ms.value
 

@@ -108,6 +108,17 @@ def lib() -> ctypes.CDLL:
             u64p, ctypes.c_size_t,
             ctypes.POINTER(ctypes.c_int32), u64p,
         ]
+        L.tn_plan_slices.restype = ctypes.c_int
+        L.tn_plan_slices.argtypes = [
+            ctypes.c_int, u64p, u64p, u64p, ctypes.c_size_t,
+            u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
+            u64p, u64p, u64p,
+        ]
+        L.tn_net_contract_sliced.restype = ctypes.c_int
+        L.tn_net_contract_sliced.argtypes = [
+            ctypes.c_void_p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
+            u64p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double),
+        ]
         _lib = L
     return _lib
 
@@ -179,6 +190,31 @@ def plan_layouts(leaves, steps, dtype="c128"):
     )
     check(rc, "tn_plan_layouts")
     return list(scatter), list(inline)
+
+
+def plan_slices(leaves, steps, slice_labels, dtype="c128"):
+    """The slice plan of tn_net_contract_sliced (tn_plan_slices). leaves and
+    steps as for plan_layouts. Returns (nassign, reduced_nd[], strides):
+    the number of assignments, each leaf's rank without the slice labels,
+    and strides[leaf][label], the element stride of each slice label in the
+    stored leaf (0 where absent). Assignment t decodes with the first label
+    most significant. Raises on a refused plan. Needs no GPU."""
+    nl, ns = len(leaves), len(slice_labels)
+    nassign = ctypes.c_uint64()
+    reduced = (ctypes.c_uint64 * nl)()
+    strides = (ctypes.c_uint64 * max(nl * ns, 1))()
+    rc = lib().tn_plan_slices(
+        {"c128": 0, "c64": 1}[dtype],
+        _u64arr([l for labels, _ in leaves for l in labels]),
+        _u64arr([d for _, dims in leaves for d in dims]),
+        _u64arr([len(labels) for labels, _ in leaves]), nl,
+        _u64arr([x for p in steps for x in p]), len(steps),
+        _u64arr(slice_labels), ns,
+        ctypes.byref(nassign), reduced, strides,
+    )
+    check(rc, "tn_plan_slices")
+    return (nassign.value, list(reduced),
+            [[strides[x * ns + y] for y in range(ns)] for x in range(nl)])
 
 
 def last_error() -> str:

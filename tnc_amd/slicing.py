@@ -146,3 +146,21 @@ def contract_sliced_gpu(tn: CompositeTensor, replace_path, edges,
             assert legs == legs_out
             total += data
     return legs_out, total
+
+
+def contract_sliced_device(tn: CompositeTensor, replace_path, edges,
+                           device: int = 0, dtype: str = "c128", which=None):
+    """Like contract_sliced_gpu, with one engine: the leaves are uploaded
+    once, every assignment is the same on-device walk over leaves sliced on
+    the device, and the sum is taken there too (tn_net_contract_sliced).
+    `which` lists assignment indices (the order of iter_assignments; None =
+    all): the result is their sum in that order. Returns (legs, ndarray)."""
+    from .executor import ContractionEngine
+
+    eng = ContractionEngine(tn, replace_path, device, dtype,
+                            slice_edges=list(edges))
+    try:
+        eng.contract_sliced(which)
+        return eng.result()
+    finally:
+        eng.close()
