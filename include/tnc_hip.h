@@ -136,6 +136,13 @@ typedef struct tn_step_plan {
   int32_t scatter_out;
   /* the 3M kernel runs its pipelined main loop (TN_GEMM3M_PIPE) */
   int32_t gemm_pipe;
+  /* the permute kernel of each pack / unpack: 0 none, 1 k_permute_ct (index
+   * gather), 2 k_permute_tile (tiled bit permutation). perm_a / perm_b /
+   * perm_out: the serial path's pack of A, pack of B and out permute.
+   * pipe_perm_a / pipe_perm_b: the window permutes of a pipelined step (0
+   * when pipe_p == 0; pipe_perm_b is 0 when B is ready). */
+  int32_t perm_a, perm_b, perm_out;
+  int32_t pipe_perm_a, pipe_perm_b;
 } tn_step_plan;
 
 /* Plan the step tn_einsum_*_dev would run on these operands (dtype 0 =

@@ -1,9 +1,11 @@
 """GPU einsum parity vs the oracle through the C ABI (tn_einsum_c128).
 
-Covers every kernel class: smallk (gate-apply shapes), anyk (skinny),
-dot (scalar out), outer product (K=1), MFMA GEMM, ragged GEMM (v1), packed
-and pack-free operands, unpack (caller-chosen out order), strided views,
-pow2 and non-pow2 dims.
+Covers smallk (gate-apply shapes), anyk (skinny), dot (scalar out), outer
+product (K=1), MFMA GEMM (pure and ragged), packed and pack-free operands
+and the unpack (caller-chosen out order) through k_permute_ct, strided
+views, pow2 and non-pow2 dims. The VALU GEMM k_zgemm_v1 and the tiled
+permute k_permute_tile are not reached by any shape here: their cases, each
+with the plan it must get, are in test_gpu_kernel_reach.py.
 """
 
 import numpy as np
@@ -20,6 +22,17 @@ def _rand(shape, rng):
     return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(
         np.complex128
     )
+
+
+def plan_of(out_labels, a_labels, a_shape, b_labels, b_shape, dtype="c128"):
+    """The plan hiplib.einsum_c128 / einsum_c64 gets for contiguous
+    operands."""
+    from tnc_amd import hiplib
+
+    dim = dict(zip(list(a_labels) + list(b_labels),
+                   list(a_shape) + list(b_shape)))
+    return hiplib.plan_step(out_labels, [dim[l] for l in out_labels],
+                            a_labels, a_shape, b_labels, b_shape, dtype=dtype)
 
 
 def run_case(a_labels, a_shape, b_labels, b_shape, seed=0, out_labels=None,
@@ -107,9 +120,17 @@ def test_gemm_mfma_qubit_legs():
     run_case(a_labels, [2] * 18, b_labels, [2] * 17, rtol=1e-11)
 
 
-def test_gemm_ragged_v1():
-    # non-pow2 dims -> v1 kernel with bounds handling
+def test_gemm_ragged_gather_and_glds():
+    """Non-pow2 2-D shapes: K = 9 <= 64 takes the gather route, and
+    67 x 130 x 41 the ragged c128 MFMA GEMM (k_zgemm_c128_glds). Neither
+    reaches k_zgemm_v1 (test_gpu_kernel_reach.py does)."""
+    from tnc_amd import hiplib as H
+
+    p = plan_of([0, 2], [0, 1], [100, 9], [1, 2], [9, 75])
+    assert p.route == H.ROUTE_GATHER
     run_case([0, 1], [100, 9], [1, 2], [9, 75])
+    p = plan_of([0, 2], [0, 1], [67, 130], [1, 2], [130, 41])
+    assert (p.route, p.kernel) == (H.ROUTE_TTGT, H.GEMM_C128_GLDS)
     run_case([0, 1], [67, 130], [1, 2], [130, 41])
 
 
@@ -346,8 +367,10 @@ def test_permute_scalar_b_exact_c64():
 
 def _exact_permute_identity_b(m_dims, k_dims, seed, c64=False):
     """A contracted with an identity over its K legs is a pure permutation:
-    the TTGT path (pack permutes k_permute_ct/k_permute_tile, MFMA GEMM,
-    split-K, unpack) must reproduce A's transpose bit-for-bit."""
+    the TTGT path (both packs and the unpack through k_permute_ct, MFMA
+    GEMM, split-K) must reproduce A's transpose bit-for-bit. Every permute
+    here is under 2^20 elements, so none is the tiled k_permute_tile (its
+    exact cases: test_gpu_kernel_reach.py); the plan is asserted."""
     from tnc_amd import hiplib
 
     rng = np.random.default_rng(seed)
@@ -378,6 +401,10 @@ def _exact_permute_identity_b(m_dims, k_dims, seed, c64=False):
             out_labels.append(n_labels[nk - 1 - i])
         if i < nm:
             out_labels.append(m_labels[i])
+    p = plan_of(out_labels, a_labels, a_dims, b_labels, list(b.shape),
+                dtype="c64" if c64 else "c128")
+    assert p.route == hiplib.ROUTE_TTGT and p.kind == 3
+    assert (p.perm_a, p.perm_b, p.perm_out) == (hiplib.PERM_CT,) * 3
     fn = hiplib.einsum_c64 if c64 else hiplib.einsum_c128
     got = fn(out_labels, a_labels, a, b_labels, b)
     # expected: A with K legs relabeled to N, transposed to the out order
@@ -394,7 +421,8 @@ def test_permute_identity_b_gemm_exact_nonpow2():
 
 
 def test_permute_identity_b_gemm_exact_pow2():
-    # all dims 2, m = 256, n = k = 256: the bit-permutation tiled path
+    # all dims 2, m = 256, n = k = 256: pure MFMA GEMM with split-K; the
+    # 2^16-element permutes go through k_permute_ct<true>
     _exact_permute_identity_b([2] * 8, [2] * 8, seed=22)
 
 

@@ -157,6 +157,9 @@ def test_ttgt_pack_a():
     assert p.route == H.ROUTE_TTGT
     assert p.pack_a and not p.pack_b
     assert p.ws_pack_a == 128 * 16 * 16 and p.ws_pack_b == 0
+    # a 2^11-element pack goes through the gather permute
+    assert (p.perm_a, p.perm_b, p.perm_out) == (H.PERM_CT, 0, 0)
+    assert (p.pipe_perm_a, p.pipe_perm_b) == (0, 0)
 
 
 def test_ttgt_out_permute():
@@ -167,6 +170,7 @@ def test_ttgt_out_permute():
     assert p.route == H.ROUTE_TTGT
     assert not p.direct and p.kind == 3
     assert p.ws_tmp_c == 128 * 64 * 16
+    assert (p.perm_a, p.perm_b, p.perm_out) == (0, 0, H.PERM_CT)
 
 
 def test_invalid_operands():

@@ -2,7 +2,9 @@
 //
 // plan_step() maps (dtype, out order, operand shapes/strides, environment) to
 // a StepPlan: route (dot / gather / TTGT), which operands get packed, the
-// pack-pipeline windows, split-K, the GEMM kernel and the workspace the step
+// pack-pipeline windows, split-K, the GEMM kernel, the permute kernel of
+// every pack and unpack (plan_permute_tile: k_permute_tile or k_permute_ct,
+// over the axis lists the executor launches with) and the workspace the step
 // will ask for. No HIP call, no HIP header: it builds with a plain host
 // compiler and runs without a GPU. The executor (einsum_dev_impl), the walk
 // plan of a whole path (plan_layouts, below: stored orders and look-ahead
@@ -43,7 +45,17 @@ typedef int64_t i64;
 #define TN_DOT_TILE_BITS (TN_DOT_TILE_ABITS + TN_DOT_TILE_BBITS)
 #define TN_DOT_MAXBITS 34
 
-#define GT 64         // k_zgemm_v1 tile edge; column-tile width of every GEMM
+// k_permute_tile: 6 a-bits (lane index of the coalesced read) + 5 b-bits
+// (lane index of the coalesced write) per block, the rest one block per
+// combination.
+#define TN_PERM_AB 6
+// BB=5 (64x32 tiles, 32 KB LDS -> more blocks/CU) measured 5.2 TB/s vs
+// 4.3 TB/s at 6/6 on the rqc36-interleave shape and holds 5.2 on bit
+// reversal (scripts/perm_tune.hip scan, r02)
+#define TN_PERM_BB 5
+#define TN_PERM_MAXBITS 34
+
+#define GT 64        // k_zgemm_v1 tile edge; column-tile width of every GEMM
 #define MF_T 128      // MFMA tile rows = MF_WAVES * 16
 #define MF_TN 64      // MFMA tile cols
 #define MF_K 16
@@ -59,8 +71,17 @@ struct DotPerm {
   u64 aB[TN_DOT_TILE_ABITS];  // B strides of the a-bits (A strides are 1<<i)
 };
 
+struct PermPerm {
+  int rbits;
+  u64 restS[TN_PERM_MAXBITS];  // src / dst element strides of each rest bit
+  u64 restD[TN_PERM_MAXBITS];
+  u64 bS[TN_PERM_BB];  // src strides of the b-bits
+  u64 bD[TN_PERM_BB];  // dst strides of the b-bits (ascending)
+  u64 aD[TN_PERM_AB];  // dst strides of the a-bits (src strides are 1<<i)
+};
+
 struct GatherGemmMap {
-  int rbits, kbits;   // bits of the row index (M for A / N for B) and of k
+  int rbits, kbits;  // bits of the row index (M for A / N for B) and of k
   u64 rstride[34];    // source stride (elements) contributed by row bit b
   u64 kstride[34];    // source stride contributed by k bit b
 };
@@ -229,6 +250,128 @@ inline int plan_dot_tile(const Meta& A, const Meta& B, const AxisList& k_a,
   }
   dp->rbits = nr;
   return nr;
+}
+
+// Tiled bit-permutation copy (k_permute_tile): the axis list (outer..inner,
+// dim and source stride; the destination is contiguous row-major over it)
+// describes a pow2 bit permutation of >= 2^20 elements whose lowest source
+// strides are coalescible. Fills *pp and returns the number of rest bits (one
+// block per combination), or -1: the permute then runs through the gather
+// permute k_permute_ct (strided views, non-pow2, tiny sizes).
+inline int plan_permute_tile(const std::vector<AxisInfo>& ax, u64 elems,
+                             PermPerm* pp) {
+  if (elems < (1ull << 20) || elems > (1ull << TN_PERM_MAXBITS)) return -1;
+  struct BitSD {
+    u64 ss, sd;
+  };
+  std::vector<BitSD> bits;
+  u64 dstride = 1;
+  for (int i = (int)ax.size() - 1; i >= 0; --i) {
+    const AxisInfo& a = ax[i];
+    if (a.dim == 1) continue;  // contributes no bits; stride irrelevant
+    if ((a.dim & (a.dim - 1)) || a.sa <= 0) return -1;
+    for (u64 d = 1; d < a.dim; d <<= 1)
+      bits.push_back({(u64)a.sa * d, dstride * d});
+    dstride *= a.dim;
+  }
+  const int nb = (int)bits.size();
+  if (nb <= TN_PERM_AB + TN_PERM_BB || (1ull << nb) != elems) return -1;
+  std::vector<int> byS(nb), byD(nb);
+  for (int i = 0; i < nb; ++i) byS[i] = byD[i] = i;
+  std::sort(byS.begin(), byS.end(),
+            [&](int x, int y) { return bits[x].ss < bits[y].ss; });
+  std::sort(byD.begin(), byD.end(),
+            [&](int x, int y) { return bits[x].sd < bits[y].sd; });
+  // the a-bits (lane index) must be the TN_PERM_AB lowest SOURCE strides,
+  // exactly 1..2^(AB-1), for coalesced reads. All other bits may carry
+  // ARBITRARY source strides (the kernel sums per-bit offsets), which
+  // admits sub-box permutes — e.g. the pack pipeline's K-windows, whose
+  // fixed leading legs leave gaps in the source span. The destination
+  // side is a full span by construction (suffix products above).
+  for (int i = 0; i < TN_PERM_AB; ++i)
+    if (bits[byS[i]].ss != (1ull << i)) return -1;
+  std::vector<char> used(nb, 0);
+  for (int i = 0; i < TN_PERM_AB; ++i) {
+    used[byS[i]] = 1;
+    pp->aD[i] = bits[byS[i]].sd;
+  }
+  int nbb = 0, nr = 0;
+  for (int i = 0; i < nb && nbb < TN_PERM_BB; ++i) {
+    const int bi = byD[i];
+    if (used[bi]) continue;
+    pp->bS[nbb] = bits[bi].ss;
+    pp->bD[nbb] = bits[bi].sd;
+    used[bi] = 1;
+    ++nbb;
+  }
+  for (int i = 0; i < nb; ++i) {
+    if (used[byS[i]]) continue;
+    pp->restS[nr] = bits[byS[i]].ss;
+    pp->restD[nr] = bits[byS[i]].sd;
+    ++nr;
+  }
+  pp->rbits = nr;
+  return nr;
+}
+
+// Which permute kernel launch_permute runs for this axis list
+// (tn_step_plan's perm_* fields): 2 k_permute_tile, 1 k_permute_ct.
+inline int permute_kind(const std::vector<AxisInfo>& ax, u64 elems) {
+  PermPerm pp;
+  return plan_permute_tile(ax, elems, &pp) >= 0 ? 2 : 1;
+}
+
+// The axis lists of a TTGT step's permutes. plan_step (the perm_* fields)
+// and the executor (the launches) both build them here, so the plan and the
+// launch cannot disagree.
+// Pack of an operand into its GEMM layout (axes = a_axes / b_axes):
+inline std::vector<AxisInfo> pack_axis_info(const Meta& t,
+                                            const AxisList& axes) {
+  std::vector<AxisInfo> ax;
+  for (int axis : axes) ax.push_back({t.dims[axis], t.strides[axis], 0});
+  return ax;
+}
+
+// Out permute: temporary C = [M legs (out order)][N legs (out order)] -> out
+// order; the source stride of each out axis is its stride inside C.
+inline std::vector<AxisInfo> out_axis_info(const StepPlan& p,
+                                           const u64* out_shape, int out_nd) {
+  std::vector<i64> tmp_stride(out_nd, 0);
+  i64 stride = 1;
+  for (int t = p.n_out.n - 1; t >= 0; --t) {
+    tmp_stride[p.n_out[t]] = stride;
+    stride *= (i64)out_shape[p.n_out[t]];
+  }
+  for (int t = p.m_out.n - 1; t >= 0; --t) {
+    tmp_stride[p.m_out[t]] = stride;
+    stride *= (i64)out_shape[p.m_out[t]];
+  }
+  std::vector<AxisInfo> ax;
+  for (int i = 0; i < out_nd; ++i)
+    ax.push_back({out_shape[i], tmp_stride[i], 0});
+  return ax;
+}
+
+// K-window packs of a pipelined step: the operand's GEMM layout without the
+// first npre K legs (those select the window).
+inline std::vector<AxisInfo> window_a_axis_info(const StepPlan& p,
+                                                const Meta& A, int npre) {
+  std::vector<AxisInfo> ax;
+  for (int o : p.m_out)
+    ax.push_back({A.dims[p.apos[o]], A.strides[p.apos[o]], 0});
+  for (int x = npre; x < p.k_a.n; ++x)
+    ax.push_back({A.dims[p.k_a[x]], A.strides[p.k_a[x]], 0});
+  return ax;
+}
+
+inline std::vector<AxisInfo> window_b_axis_info(const StepPlan& p,
+                                                const Meta& B, int npre) {
+  std::vector<AxisInfo> ax;
+  for (int x = npre; x < p.k_b.n; ++x)
+    ax.push_back({B.dims[p.k_b[x]], B.strides[p.k_b[x]], 0});
+  for (int o : p.n_out)
+    ax.push_back({B.dims[p.bpos[o]], B.strides[p.bpos[o]], 0});
+  return ax;
 }
 
 // Build the bit-scatter map of a packed [row][k] (or [k][col]) layout:
@@ -573,6 +716,21 @@ inline int plan_step(bool c128, const u64* out_labels, const u64* out_shape,
   p.ws_pack_b = (packs && p.pack_b) ? K * N * esize : 0;
   p.ws_slices = (u64)p.pipe_p * nout * esize;
   p.ws_split = (!p.pipe_p && p.splitk > 1) ? p.splitk * nout * esize : 0;
+
+  // which permute kernel each pack / unpack launches
+  if (!p.gather_gemm && p.pack_a)
+    p.perm_a = permute_kind(pack_axis_info(A, p.a_axes), M * K);
+  if (!p.gather_gemm && p.pack_b)
+    p.perm_b = permute_kind(pack_axis_info(B, p.b_axes), K * N);
+  if (!p.direct && !p.scatter_out)
+    p.perm_out = permute_kind(out_axis_info(p, out_shape, out_nd), nout);
+  if (p.pipe_p) {
+    p.pipe_perm_a = permute_kind(window_a_axis_info(p, A, p.pipe_npre),
+                                 M * p.pipe_kc);
+    if (p.pack_b)
+      p.pipe_perm_b = permute_kind(window_b_axis_info(p, B, p.pipe_npre),
+                                   p.pipe_kc * N);
+  }
   return TN_OK;
 }
 

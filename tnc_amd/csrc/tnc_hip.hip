@@ -206,21 +206,7 @@ __global__ void k_einsum_anyk(const CT* __restrict__ A,
 // lane index of a coalesced READ and the 6 lowest free dst bits the lane
 // index of a coalesced WRITE, staged through a 64x64 XOR-swizzled LDS tile
 // (64 KB c128 -> 2 blocks/CU).
-#define TN_PERM_AB 6
-// BB=5 (64x32 tiles, 32 KB LDS -> more blocks/CU) measured 5.2 TB/s vs
-// 4.3 TB/s at 6/6 on the rqc36-interleave shape and holds 5.2 on bit
-// reversal (scripts/perm_tune.hip scan, r02)
-#define TN_PERM_BB 5
-#define TN_PERM_MAXBITS 34
-
-struct PermPerm {
-  int rbits;
-  u64 restS[TN_PERM_MAXBITS];  // src / dst element strides of each rest bit
-  u64 restD[TN_PERM_MAXBITS];
-  u64 bS[TN_PERM_BB];  // src strides of the b-bits
-  u64 bD[TN_PERM_BB];  // dst strides of the b-bits (ascending)
-  u64 aD[TN_PERM_AB];  // dst strides of the a-bits (src strides are 1<<i)
-};
+// (TN_PERM_*, PermPerm and plan_permute_tile: step_plan.hpp)
 
 template <typename CT>
 __global__ __launch_bounds__(512) void k_permute_tile(
@@ -1573,76 +1559,18 @@ static void ws_free(WsCtx& ctx, void* p) {
   (void)hipFree(p);  // hipFree device-syncs before releasing the pages
 }
 
-// Launch the tiled permute when the axis list describes a pow2 full-span
-// bit permutation (contiguous source, >= 2^20 elements); returns false to
-// fall back to the gather permute (strided views, non-pow2, tiny sizes).
-template <typename CT>
-static bool permute_tiled(const CT* src, CT* dst, u64 elems,
-                          const std::vector<AxisInfo>& ax,
-                          hipStream_t stream) {
-  if (elems < (1ull << 20) || elems > (1ull << TN_PERM_MAXBITS)) return false;
-  struct BitSD {
-    u64 ss, sd;
-  };
-  std::vector<BitSD> bits;
-  u64 dstride = 1;
-  for (int i = (int)ax.size() - 1; i >= 0; --i) {
-    const AxisInfo& a = ax[i];
-    if (a.dim == 1) continue;  // contributes no bits; stride irrelevant
-    if ((a.dim & (a.dim - 1)) || a.sa <= 0) return false;
-    for (u64 d = 1; d < a.dim; d <<= 1)
-      bits.push_back({(u64)a.sa * d, dstride * d});
-    dstride *= a.dim;
-  }
-  const int nb = (int)bits.size();
-  if (nb <= TN_PERM_AB + TN_PERM_BB || (1ull << nb) != elems) return false;
-  std::vector<int> byS(nb), byD(nb);
-  for (int i = 0; i < nb; ++i) byS[i] = byD[i] = i;
-  std::sort(byS.begin(), byS.end(),
-            [&](int x, int y) { return bits[x].ss < bits[y].ss; });
-  std::sort(byD.begin(), byD.end(),
-            [&](int x, int y) { return bits[x].sd < bits[y].sd; });
-  // the a-bits (lane index) must be the TN_PERM_AB lowest SOURCE strides,
-  // exactly 1..2^(AB-1), for coalesced reads. All other bits may carry
-  // ARBITRARY source strides (the kernel sums per-bit offsets), which
-  // admits sub-box permutes — e.g. the pack pipeline's K-windows, whose
-  // fixed leading legs leave gaps in the source span. The destination
-  // side is a full span by construction (suffix products above).
-  for (int i = 0; i < TN_PERM_AB; ++i)
-    if (bits[byS[i]].ss != (1ull << i)) return false;
-  PermPerm pp;
-  std::vector<char> used(nb, 0);
-  for (int i = 0; i < TN_PERM_AB; ++i) {
-    used[byS[i]] = 1;
-    pp.aD[i] = bits[byS[i]].sd;
-  }
-  int nbb = 0, nr = 0;
-  for (int i = 0; i < nb && nbb < TN_PERM_BB; ++i) {
-    const int bi = byD[i];
-    if (used[bi]) continue;
-    pp.bS[nbb] = bits[bi].ss;
-    pp.bD[nbb] = bits[bi].sd;
-    used[bi] = 1;
-    ++nbb;
-  }
-  for (int i = 0; i < nb; ++i) {
-    if (used[byS[i]]) continue;
-    pp.restS[nr] = bits[byS[i]].ss;
-    pp.restD[nr] = bits[byS[i]].sd;
-    ++nr;
-  }
-  pp.rbits = nr;
-  k_permute_tile<<<dim3(1u << nr), 512, 0, stream>>>(src, dst, pp);
-  return true;
-}
-
-// Launch the best permute kernel for a gather described by `ax` (tiled
-// bit-permutation when applicable, else the index-gather permute).
+// Launch the permute kernel plan_permute_tile (step_plan.hpp) chooses for a
+// gather described by `ax`: the tiled bit permutation when it applies, else
+// the index-gather permute.
 template <typename CT>
 static int launch_permute(const CT* src, CT* dst, u64 elems,
                           const std::vector<AxisInfo>& ax,
                           hipStream_t stream) {
-  if (!permute_tiled(src, dst, elems, ax, stream)) {
+  PermPerm pp;
+  const int nr = plan_permute_tile(ax, elems, &pp);
+  if (nr >= 0) {
+    k_permute_tile<<<dim3(1u << nr), 512, 0, stream>>>(src, dst, pp);
+  } else {
     GatherMap map;
     if (build_map(ax, &map)) FAILV(TN_ERR_INVALID, "rank too large");
     int blocks = grid_for(elems);
@@ -1862,23 +1790,15 @@ static int ttgt_pipelined(const Step<CT>& s, CT* Cg, bool* done) {
       offB += digit * (u64)B.strides[p.k_b[x]];
     }
     {
-      std::vector<AxisInfo> ax;
-      for (int o : p.m_out)
-        ax.push_back({A.dims[p.apos[o]], A.strides[p.apos[o]], 0});
-      for (int x = npre; x < p.k_a.n; ++x)
-        ax.push_back({A.dims[p.k_a[x]], A.strides[p.k_a[x]], 0});
       int prc = launch_permute(s.Adata + offA, Awin.p + (u64)w * M * kc,
-                               M * kc, ax, s.ws.stream2);
+                               M * kc, window_a_axis_info(p, A, npre),
+                               s.ws.stream2);
       if (prc) return prc;
     }
     if (p.pack_b) {
-      std::vector<AxisInfo> ax;
-      for (int x = npre; x < p.k_b.n; ++x)
-        ax.push_back({B.dims[p.k_b[x]], B.strides[p.k_b[x]], 0});
-      for (int o : p.n_out)
-        ax.push_back({B.dims[p.bpos[o]], B.strides[p.bpos[o]], 0});
       int prc = launch_permute(s.Bdata + offB, Bwin.p + (u64)w * kc * N,
-                               kc * N, ax, s.ws.stream2);
+                               kc * N, window_b_axis_info(p, B, npre),
+                               s.ws.stream2);
       if (prc) return prc;
     }
     HIP_CHECK(hipEventRecord(ev.ep[w], s.ws.stream2));
@@ -1925,10 +1845,10 @@ static int ttgt_serial(const Step<CT>& s, CT* Cg, WsBlock<CT>& packA,
   const CT* Bg = s.Bdata;
   auto pack = [&](const Meta& t, const AxisList& axes, u64 elems,
                   WsBlock<CT>& blk, const CT** src) -> int {
-    std::vector<AxisInfo> ax;
-    for (int axis : axes) ax.push_back({t.dims[axis], t.strides[axis], 0});
     if (int rc_ = blk.alloc(elems * sizeof(CT))) return rc_;
-    if (int rc_ = launch_permute(*src, blk.p, elems, ax, s.stream)) return rc_;
+    if (int rc_ = launch_permute(*src, blk.p, elems, pack_axis_info(t, axes),
+                                 s.stream))
+      return rc_;
     *src = blk.p;
     return TN_OK;
   };
@@ -2021,21 +1941,8 @@ static int run_ttgt(const Step<CT>& s) {
   // the (slower) gather kernels instead of failing the whole contraction
   if (rc_ == TN_ERR_OOM && p.gather_ok) return run_gather(s);
   if (rc_ || to_out) return rc_;
-  // permute tmp [M legs (out order)][N legs (out order)] -> out order;
-  // source strides of each out axis inside tmp:
-  std::vector<i64> tmp_stride(s.out_nd, 0);
-  i64 stride = 1;
-  for (int t = p.n_out.n - 1; t >= 0; --t) {
-    tmp_stride[p.n_out[t]] = stride;
-    stride *= (i64)s.out_shape[p.n_out[t]];
-  }
-  for (int t = p.m_out.n - 1; t >= 0; --t) {
-    tmp_stride[p.m_out[t]] = stride;
-    stride *= (i64)s.out_shape[p.m_out[t]];
-  }
-  std::vector<AxisInfo> ax;
-  for (int i = 0; i < s.out_nd; ++i)
-    ax.push_back({s.out_shape[i], tmp_stride[i], 0});
+  // permute tmp [M legs (out order)][N legs (out order)] -> out order
+  const std::vector<AxisInfo> ax = out_axis_info(p, s.out_shape, s.out_nd);
   return launch_permute((const CT*)tmpC.p, s.out, p.nout(), ax, s.stream);
 }
 

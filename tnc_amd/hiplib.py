@@ -144,6 +144,9 @@ class StepPlan(ctypes.Structure):
         ("ws_split", ctypes.c_uint64), ("ws_dot", ctypes.c_uint64),
         ("scatter_out", ctypes.c_int32),
         ("gemm_pipe", ctypes.c_int32),
+        ("perm_a", ctypes.c_int32), ("perm_b", ctypes.c_int32),
+        ("perm_out", ctypes.c_int32),
+        ("pipe_perm_a", ctypes.c_int32), ("pipe_perm_b", ctypes.c_int32),
     ]
 
 
@@ -151,6 +154,7 @@ ROUTE_DOT, ROUTE_GATHER, ROUTE_TTGT = 0, 1, 2
 DOT_LINEAR, DOT_TILED, DOT_GATHER = 0, 1, 2
 (GEMM_V1, GEMM_MFMA, GEMM_C128_GLDS, GEMM_C128_PURE, GEMM_C128_3M,
  GEMM_C128_GATHER, GEMM_C64_PURE) = range(7)
+PERM_NONE, PERM_CT, PERM_TILE = 0, 1, 2  # perm_* / pipe_perm_* fields
 
 
 def plan_step(out_labels, out_shape, a_labels, a_shape, b_labels, b_shape,
