@@ -192,6 +192,106 @@ int tn_plan_slices(int dtype, const uint64_t* leaf_labels,
                    uint64_t* nassign, uint64_t* reduced_nd,
                    uint64_t* strides);
 
+/* --------------------------- batch labels ----------------------------- */
+
+/* A batch label is carried by both operands of a step AND kept in out, not
+ * summed: out[b.., m.., n..] = sum_k A[b.., m.., k..] * B[b.., k.., n..].
+ * The caller lists the labels that may act so (batch_labels). A listed label
+ * found in both operands is a step-batch label: it must appear in out with
+ * the same dim, and the step-batch labels must be the leading axes of out
+ * (any order among themselves), so one batch element of out is contiguous. A
+ * listed label found in one operand only is an ordinary free label; a label
+ * in both operands that is not listed is contracted, as everywhere else. */
+enum { TN_BATCH_NONE = 0, TN_BATCH_GATHER = 1, TN_BATCH_GEMM = 2,
+       TN_BATCH_LOOP = 3 };
+
+typedef struct tn_batch_plan {
+  uint64_t batch;       /* product of the step-batch dims; 1 = none */
+  int32_t cls;          /* TN_BATCH_* */
+  uint64_t dispatches;  /* compute dispatches: 1 for GATHER/GEMM, batch for LOOP */
+  uint64_t ws_pack_a, ws_pack_b; /* batched pack buffers (GEMM class), 0 if ready */
+  tn_step_plan elem;    /* plan of one batch element (whole step when NONE) */
+} tn_batch_plan;
+
+/* Plan the step tn_einsum_*_batched_dev would run. Arguments as tn_plan_step
+ * plus the batch labels. TN_BATCH_NONE: no step-batch label, elem is
+ * tn_plan_step's plan of the same operands. TN_BATCH_GATHER: the element is on
+ * the gather route; one launch of the gather kernels covers all of out.
+ * TN_BATCH_GEMM: the element is an unsplit TTGT GEMM of fewer than 256 tiles;
+ * operands are packed to [batch][M][K] / [batch][K][N] where they are not in
+ * that order already and one launch of the batched MFMA kernel computes every
+ * element (TN_BATCH_GEMM=0 in the environment turns this class into LOOP).
+ * TN_BATCH_LOOP: the element step runs `batch` times on offset views. Needs
+ * no GPU. */
+int tn_plan_step_batched(int dtype, const uint64_t* out_labels,
+                         const uint64_t* out_shape, size_t out_ndim,
+                         const uint64_t* a_labels, const uint64_t* a_shape,
+                         const int64_t* a_strides, size_t a_ndim,
+                         const uint64_t* b_labels, const uint64_t* b_shape,
+                         const int64_t* b_strides, size_t b_ndim,
+                         const uint64_t* batch_labels, size_t nbatch,
+                         int has_stream2, tn_batch_plan* plan);
+
+/* The walk plan of tn_net_contract_batched: leaves and path as for
+ * tn_plan_layouts, plus the batch labels. Step s stores its output as
+ * [batch labels carried by both operands, in batch_labels order][A-only legs
+ * in A order][B-only legs in B order]. cls[nsteps] gets each step's
+ * TN_BATCH_* class, out_nd[nsteps] the rank of its output, out_labels
+ * (nsteps rows of 64) the labels in stored order, ws_bytes[nsteps] the
+ * workspace the step asks for beyond its output. Any output may be NULL.
+ * Returns TN_ERR_INVALID, with the text in tn_last_error, for a path or rank
+ * tn_plan_layouts refuses and for a batch label that is listed twice, is in
+ * no leaf or has differing dims across leaves. Needs no GPU. */
+int tn_plan_batch_walk(int dtype, const uint64_t* leaf_labels,
+                       const uint64_t* leaf_dims, const uint64_t* leaf_nd,
+                       size_t nleaves, const uint64_t* pairs, size_t nsteps,
+                       const uint64_t* batch_labels, size_t nbatch,
+                       int32_t* cls, uint64_t* out_nd, uint64_t* out_labels,
+                       uint64_t* ws_bytes);
+
+/* Batched einsum: tn_einsum_* with batch labels (semantics above). */
+int tn_einsum_c128_batched(const uint64_t* out_labels,
+                           const uint64_t* out_shape, size_t out_ndim,
+                           const uint64_t* a_labels, const uint64_t* a_shape,
+                           const int64_t* a_strides, const void* a_data,
+                           size_t a_ndim, const uint64_t* b_labels,
+                           const uint64_t* b_shape, const int64_t* b_strides,
+                           const void* b_data, size_t b_ndim,
+                           const uint64_t* batch_labels, size_t nbatch,
+                           void* out_data);
+
+int tn_einsum_c64_batched(const uint64_t* out_labels,
+                          const uint64_t* out_shape, size_t out_ndim,
+                          const uint64_t* a_labels, const uint64_t* a_shape,
+                          const int64_t* a_strides, const void* a_data,
+                          size_t a_ndim, const uint64_t* b_labels,
+                          const uint64_t* b_shape, const int64_t* b_strides,
+                          const void* b_data, size_t b_ndim,
+                          const uint64_t* batch_labels, size_t nbatch,
+                          void* out_data);
+
+int tn_einsum_c128_batched_dev(const uint64_t* out_labels,
+                               const uint64_t* out_shape, size_t out_ndim,
+                               const uint64_t* a_labels,
+                               const uint64_t* a_shape,
+                               const int64_t* a_strides, const void* a_dev,
+                               size_t a_ndim, const uint64_t* b_labels,
+                               const uint64_t* b_shape,
+                               const int64_t* b_strides, const void* b_dev,
+                               size_t b_ndim, const uint64_t* batch_labels,
+                               size_t nbatch, void* out_dev, void* stream);
+
+int tn_einsum_c64_batched_dev(const uint64_t* out_labels,
+                              const uint64_t* out_shape, size_t out_ndim,
+                              const uint64_t* a_labels,
+                              const uint64_t* a_shape,
+                              const int64_t* a_strides, const void* a_dev,
+                              size_t a_ndim, const uint64_t* b_labels,
+                              const uint64_t* b_shape,
+                              const int64_t* b_strides, const void* b_dev,
+                              size_t b_ndim, const uint64_t* batch_labels,
+                              size_t nbatch, void* out_dev, void* stream);
+
 /* ------------ network executor (contract_tensor_network) ------------- */
 
 typedef struct tn_net tn_net;
@@ -249,6 +349,19 @@ int tn_net_contract_sliced(tn_net* net, const uint64_t* pairs, size_t nsteps,
                            const uint64_t* slice_labels, size_t nlabels,
                            const uint64_t* which, size_t nwhich,
                            double* elapsed_ms);
+
+/* Contract along the path keeping the listed batch labels: a label of
+ * batch_labels carried by several leaves is never summed, and the final
+ * tensor keeps it (one amplitude per bitstring when the bras are [B, 2]
+ * leaves sharing one label). Stored orders and step classes are those of
+ * tn_plan_batch_walk; there is no look-ahead pack, no scatter epilogue and
+ * no hipGraph capture in this walk. The walk plan and the captured graph
+ * tn_net_contract keeps for the net are left as they are, so the two calls
+ * may alternate on one net. nbatch == 0 gives the final tensor of
+ * tn_net_contract. Results are read with tn_net_result_*. */
+int tn_net_contract_batched(tn_net* net, const uint64_t* pairs, size_t nsteps,
+                            const uint64_t* batch_labels, size_t nbatch,
+                            double* elapsed_ms);
 
 /* Synchronous device-to-device copy on the current device (for exchanging
  * buffers with an external allocator, e.g. RCCL-communicated tensors). */

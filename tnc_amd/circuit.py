@@ -154,6 +154,48 @@ class Circuit:
             self.tensor_network.push_tensor(t)
         return self.tensor_network, Permutor(final_legs)
 
+    def into_amplitudes_network(self, bitstrings):
+        """The network of MANY amplitudes in one walk: like
+        into_amplitude_network, but a qubit whose bit differs between the
+        bitstrings gets a bra leaf with legs [beta, edge] and dims [B, 2],
+        row r the bra of bitstrings[r]; beta is a fresh edge shared by all
+        those leaves (a batch label: kept, never summed). A qubit whose bit
+        is the same everywhere gets the ordinary rank-1 bra, '*' leaves the
+        edge open (same positions in every bitstring). Leaf order is that of
+        into_amplitude_network, so a path found on a single-bitstring network
+        of the same circuit is valid, and slicing.slice_network(tn, {beta:
+        r}) is bitstring r's ordinary network. Returns (tn, Permutor, beta);
+        contract with executor.amplitudes_gpu."""
+        bitstrings = list(bitstrings)
+        if not bitstrings:
+            raise ValueError("no bitstring given")
+        n = self.num_qubits()
+        for b in bitstrings:
+            if len(b) != n:
+                raise ValueError("bitstrings must have one character per qubit")
+            if set(b) - set("01*"):
+                raise ValueError("Only 0, 1 and * are allowed in bitstring")
+            if [c == "*" for c in b] != [c == "*" for c in bitstrings[0]]:
+                raise ValueError("'*' must be in the same positions of every "
+                                 "bitstring")
+        beta = self._new_edge()
+        final_legs = []
+        for q, e in enumerate(self.open_edges):
+            column = [b[q] for b in bitstrings]
+            if column[0] == "*":
+                final_legs.append(e)
+            elif len(set(column)) == 1:
+                t = LeafTensor.new_from_const([e], 2)
+                t.set_tensor_data(_ket0() if column[0] == "0" else _ket1())
+                self.tensor_network.push_tensor(t)
+            else:
+                rows = np.zeros((len(bitstrings), 2), dtype=np.complex128)
+                rows[np.arange(len(bitstrings)), [int(c) for c in column]] = 1.0
+                t = LeafTensor([beta, e], [len(bitstrings), 2])
+                t.set_tensor_data(TensorData(TensorData.MATRIX, matrix=rows))
+                self.tensor_network.push_tensor(t)
+        return self.tensor_network, Permutor(final_legs), beta
+
     def into_statevector_network(self):
         """circuit_builder.rs:270-273."""
         return self.into_amplitude_network("*" * self.num_qubits())

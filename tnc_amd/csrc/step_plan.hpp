@@ -149,21 +149,25 @@ struct AxisList {
 //                     scatter epilogue, and plan_layouts may choose a step's
 //                     stored order for its consumer; "0": neither (every
 //                     step stores the symmetric-difference order)
+//   TN_BATCH_GEMM     unset: a batched step whose element is a small unsplit
+//                     GEMM runs as one launch of k_zgemm_batched; "0": it
+//                     loops over the batch elements instead (TN_BATCH_LOOP),
+//                     the A/B handle of scripts/batch_amplitudes.py
 enum EnvSwitch { ENV_NO_PIPELINE, ENV_PIPELINE_FORCE, ENV_GATHER_GEMM,
                  ENV_GEMM3M, ENV_NO_PREPACK, ENV_EPI_SCATTER, ENV_GEMM3M_PIPE,
-                 ENV_COUNT };
+                 ENV_BATCH_GEMM, ENV_COUNT };
 enum { GEMM3M_OFF = 0, GEMM3M_GATED = 1, GEMM3M_FORCE = 2 };
 
 inline int env_switch(EnvSwitch s) {
   static const char* const names[ENV_COUNT] = {
       "TN_NO_PIPELINE", "TN_PIPELINE_FORCE", "TN_GATHER_GEMM", "TN_GEMM3M",
-      "TN_NO_PREPACK", "TN_EPI_SCATTER", "TN_GEMM3M_PIPE"};
-  static int cache[ENV_COUNT] = {-1, -1, -1, -1, -1, -1, -1};
+      "TN_NO_PREPACK", "TN_EPI_SCATTER", "TN_GEMM3M_PIPE", "TN_BATCH_GEMM"};
+  static int cache[ENV_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1};
   int& v = cache[s];
   if (v < 0) {
     const char* e = getenv(names[s]);
     const bool on = e && e[0] && e[0] != '0';
-    if (s == ENV_EPI_SCATTER || s == ENV_GEMM3M_PIPE)
+    if (s == ENV_EPI_SCATTER || s == ENV_GEMM3M_PIPE || s == ENV_BATCH_GEMM)
       v = (!e || !e[0] || on) ? 1 : 0;  // on unless "0"
     else if (s != ENV_GEMM3M)
       v = on ? 1 : 0;
@@ -1082,6 +1086,281 @@ inline void plan_slices(bool c128, const std::vector<LayoutTensor>& leaves,
     return;
   }
   sp->valid = true;
+}
+
+// ---- batch labels ---------------------------------------------------------
+// A step-batch label is carried by both operands and kept in out (not
+// summed); the caller lists the labels that may act so. plan_step_batched
+// splits those axes off, plans ONE batch element with plan_step (metas with
+// the batch axes removed, strides kept) and classifies the step:
+//   NONE    no step-batch label: the plan is plan_step's, field for field
+//   GATHER  element on the gather route: one launch of the gather kernels
+//           over all of out; a batch axis carries a stride in both operands
+//   GEMM    element is an unsplit TTGT GEMM of fewer than TN_BATCH_MAXTILES
+//           tiles: operands packed to [batch][M][K] / [batch][K][N] (one
+//           permute each, none when already so), one k_zgemm_batched launch
+//   LOOP    the rest (dot, split-K, an element that fills the device alone):
+//           the element step, `batch` times, on offset views
+// The step-batch labels lead out, so element b of out is the contiguous
+// block at out + b*M*N, b the row-major index over the batch axes in out
+// order.
+
+// one workgroup per CU of the MI355X: an element with that many tiles gains
+// nothing from sharing a launch
+#define TN_BATCH_MAXTILES 256
+#define BG_T 64  // k_zgemm_batched tile edge
+
+struct BatchPlan : tn_batch_plan {
+  StepPlan ep;                  // the element plan, with its axis lists
+  int nb = 0;                   // step-batch axes = the first nb axes of out
+  int ba[TN_MAXR], bb[TN_MAXR]; // their positions in A / B, in out order
+  u64 bdim[TN_MAXR];
+  Meta Ae, Be;                  // one element: batch axes removed
+  int a_el[TN_MAXR], b_el[TN_MAXR];  // full-operand axis of each element axis
+  // GEMM class
+  u64 row_tiles = 0, col_tiles = 0;  // BG_T x BG_T tiles of one element
+};
+
+// source offset (elements) of batch element b in an operand
+inline i64 batch_offset(const BatchPlan& p, const Meta& t, const int* pos,
+                        u64 b) {
+  i64 off = 0;
+  for (int x = p.nb - 1; x >= 0; --x) {
+    off += (i64)(b % p.bdim[x]) * t.strides[pos[x]];
+    b /= p.bdim[x];
+  }
+  return off;
+}
+
+// Pack of a whole batched operand: [batch axes in out order][element axes in
+// GEMM order]
+inline std::vector<AxisInfo> batch_pack_axis_info(const BatchPlan& p,
+                                                  const Meta& t,
+                                                  const int* pos,
+                                                  const Meta& te,
+                                                  const AxisList& axes) {
+  std::vector<AxisInfo> ax;
+  for (int x = 0; x < p.nb; ++x)
+    ax.push_back({t.dims[pos[x]], t.strides[pos[x]], 0});
+  for (int axis : axes) ax.push_back({te.dims[axis], te.strides[axis], 0});
+  return ax;
+}
+
+// Out permute of a batched GEMM: temporary [batch][M legs][N legs] -> out
+inline std::vector<AxisInfo> batch_out_axis_info(const BatchPlan& p,
+                                                 const u64* out_shape,
+                                                 int out_nd) {
+  std::vector<AxisInfo> ax(p.nb), el =
+      out_axis_info(p.ep, out_shape + p.nb, out_nd - p.nb);
+  i64 stride = (i64)p.ep.nout();
+  for (int x = p.nb - 1; x >= 0; --x) {
+    ax[x] = {p.bdim[x], stride, 0};
+    stride *= (i64)p.bdim[x];
+  }
+  ax.insert(ax.end(), el.begin(), el.end());
+  return ax;
+}
+
+inline bool axis_info_ready(const std::vector<AxisInfo>& ax) {
+  i64 stride = 1;
+  for (int i = (int)ax.size() - 1; i >= 0; --i) {
+    if (ax[i].sa != stride) return false;
+    stride *= (i64)ax[i].dim;
+  }
+  return true;
+}
+
+inline int plan_step_batched(bool c128, const u64* out_labels,
+                             const u64* out_shape, int out_nd, const Meta& A,
+                             const Meta& B, const u64* batch_labels,
+                             size_t nbatch, bool has_stream2, BatchPlan* plan,
+                             std::string* err) {
+  BatchPlan& p = *plan;
+  p = BatchPlan();
+  const u64 esize = c128 ? 16 : 8;
+  auto fail = [&](const char* fmt, u64 v) {
+    char buf[128];
+    snprintf(buf, sizeof buf, fmt, (unsigned long long)v);
+    *err = buf;
+    return (int)TN_ERR_INVALID;
+  };
+  if (A.nd > TN_MAXR || B.nd > TN_MAXR || out_nd > TN_MAXR)
+    return fail("tensor rank exceeds %llu", TN_MAXR);
+  auto find = [](const Meta& t, u64 lab) {
+    for (int i = 0; i < t.nd; ++i)
+      if (t.labels[i] == lab) return i;
+    return -1;
+  };
+  // the step-batch labels, by their position in out
+  int at_out[TN_MAXR];  // out axis -> 1 when a step-batch label sits there
+  for (int o = 0; o < out_nd; ++o) at_out[o] = 0;
+  p.batch = 1;
+  for (size_t x = 0; x < nbatch; ++x) {
+    const u64 lab = batch_labels[x];
+    bool seen = false;
+    for (size_t y = 0; y < x; ++y) seen = seen || batch_labels[y] == lab;
+    const int ia = find(A, lab), ib = find(B, lab);
+    if (seen || ia < 0 || ib < 0) continue;  // free label, or not here
+    int o = 0;
+    while (o < out_nd && out_labels[o] != lab) ++o;
+    if (o == out_nd) return fail("batch label %llu missing from out", lab);
+    if (A.dims[ia] != B.dims[ib] || A.dims[ia] != out_shape[o])
+      return fail("batch dim mismatch on label %llu", lab);
+    at_out[o] = 1;
+    ++p.nb;
+  }
+  for (int o = 0; o < p.nb; ++o) {
+    if (!at_out[o]) {
+      *err = "batch labels must lead out";
+      return (int)TN_ERR_INVALID;
+    }
+    p.ba[o] = find(A, out_labels[o]);
+    p.bb[o] = find(B, out_labels[o]);
+    p.bdim[o] = out_shape[o];
+    p.batch *= out_shape[o];
+  }
+  // one element: the operands without the step-batch axes, strides kept
+  auto strip = [&](const Meta& t, const int* pos, Meta* e, int* el) {
+    e->nd = 0;
+    e->data = t.data;
+    for (int i = 0; i < t.nd; ++i) {
+      bool is_batch = false;
+      for (int x = 0; x < p.nb; ++x) is_batch = is_batch || pos[x] == i;
+      if (is_batch) continue;
+      e->labels[e->nd] = t.labels[i];
+      e->dims[e->nd] = t.dims[i];
+      e->strides[e->nd] = t.strides[i];
+      el[e->nd++] = i;
+    }
+  };
+  strip(A, p.ba, &p.Ae, p.a_el);
+  strip(B, p.bb, &p.Be, p.b_el);
+  if (int rc = plan_step(c128, out_labels + p.nb, out_shape + p.nb,
+                         out_nd - p.nb, p.Ae, p.Be, has_stream2, &p.ep, err))
+    return rc;
+  p.elem = p.ep;
+  p.dispatches = 1;
+  p.cls = TN_BATCH_NONE;
+  if (p.nb == 0) return TN_OK;
+
+  const StepPlan& e = p.ep;
+  p.row_tiles = (e.m + BG_T - 1) / BG_T;
+  p.col_tiles = (e.n + BG_T - 1) / BG_T;
+  const u64 tiles = p.row_tiles * p.col_tiles;
+  if (e.route == TN_ROUTE_GATHER) {
+    p.cls = TN_BATCH_GATHER;
+  } else if (e.route == TN_ROUTE_TTGT && e.splitk == 1 &&
+             e.row_tiles * e.col_tiles < TN_BATCH_MAXTILES &&
+             tiles < (1ull << 31) / p.batch &&  // the grid is 32-bit
+             env_switch(ENV_BATCH_GEMM)) {
+    p.cls = TN_BATCH_GEMM;
+    if (!axis_info_ready(batch_pack_axis_info(p, A, p.ba, p.Ae, e.a_axes)))
+      p.ws_pack_a = p.batch * e.m * e.k * esize;
+    if (!axis_info_ready(batch_pack_axis_info(p, B, p.bb, p.Be, e.b_axes)))
+      p.ws_pack_b = p.batch * e.k * e.n * esize;
+  } else {
+    p.cls = TN_BATCH_LOOP;
+    p.dispatches = p.batch;
+  }
+  return TN_OK;
+}
+
+// workspace a batched step asks for beyond its output
+inline u64 batch_step_ws(const BatchPlan& p, u64 esize) {
+  const tn_step_plan& e = p.elem;
+  const u64 elem_ws = e.ws_pack_a + e.ws_pack_b + e.ws_tmp_c + e.ws_slices +
+                      e.ws_split + e.ws_dot;
+  if (p.cls == TN_BATCH_GATHER) return 0;
+  if (p.cls == TN_BATCH_GEMM)
+    return p.ws_pack_a + p.ws_pack_b +
+           (e.direct ? 0 : p.batch * e.m * e.n * esize);
+  return elem_ws;  // NONE, LOOP: one element at a time
+}
+
+// The walk plan of a batched contraction: stored order and class of every
+// step of a flat replace-left path. Order rule: [labels of L carried by both
+// operands, in L's order][A-only legs in A order][B-only legs in B order];
+// a label of L carried by one operand only counts as A-only / B-only. Every
+// batched step then writes [batch][M legs][N legs] directly. No scatter
+// epilogue, no look-ahead pack, no layout proposals.
+struct BatchWalkPlan {
+  bool valid = false;
+  std::string err;
+  std::vector<LayoutTensor> out;  // stored order of every step's output
+  std::vector<int32_t> cls;
+  std::vector<u64> ws_bytes;
+};
+
+inline void plan_batch_walk(bool c128, const std::vector<LayoutTensor>& leaves,
+                            const u64* pairs, size_t nsteps,
+                            const u64* batch_labels, size_t nbatch,
+                            BatchWalkPlan* bw) {
+  *bw = BatchWalkPlan();
+  const size_t n = leaves.size();
+  const u64 esize = c128 ? 16 : 8;
+  char buf[160];
+  auto refuse = [&](const char* fmt, u64 a) {
+    snprintf(buf, sizeof buf, fmt, (unsigned long long)a);
+    bw->err = buf;
+  };
+  for (size_t x = 0; x < nbatch; ++x) {
+    const u64 lab = batch_labels[x];
+    for (size_t y = 0; y < x; ++y)
+      if (batch_labels[y] == lab)
+        return refuse("batch label %llu is listed twice", lab);
+    u64 dim = 0;
+    for (const LayoutTensor& t : leaves)
+      for (size_t a = 0; a < t.labels.size(); ++a) {
+        if (t.labels[a] != lab) continue;
+        if (dim && t.dims[a] != dim)
+          return refuse("batch label %llu has differing dims across leaves",
+                        lab);
+        dim = t.dims[a];
+      }
+    if (!dim) return refuse("batch label %llu is in no leaf", lab);
+  }
+  for (const LayoutTensor& t : leaves)
+    if (t.labels.size() > (size_t)TN_MAXR)
+      return refuse("tensor rank exceeds %llu", TN_MAXR);
+  std::vector<LayoutTensor> stored(leaves);
+  std::vector<char> alive(n, 1);
+  bw->out.resize(nsteps);
+  bw->cls.assign(nsteps, TN_BATCH_NONE);
+  bw->ws_bytes.assign(nsteps, 0);
+  for (size_t s = 0; s < nsteps; ++s) {
+    const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
+    if (i >= n || j >= n || i == j || !alive[i] || !alive[j]) {
+      bw->err = "invalid contraction path step";
+      return;
+    }
+    const LayoutTensor &A = stored[i], &B = stored[j];
+    LayoutTensor o, rest;
+    for (size_t x = 0; x < nbatch; ++x)
+      for (size_t a = 0; a < A.labels.size(); ++a)
+        if (A.labels[a] == batch_labels[x] && layout_has(B, batch_labels[x])) {
+          o.labels.push_back(A.labels[a]);
+          o.dims.push_back(A.dims[a]);
+        }
+    layout_symdiff(A, B, &rest);
+    o.labels.insert(o.labels.end(), rest.labels.begin(), rest.labels.end());
+    o.dims.insert(o.dims.end(), rest.dims.begin(), rest.dims.end());
+    if (o.labels.size() > (size_t)TN_MAXR)
+      return refuse("tensor rank exceeds %llu", TN_MAXR);
+    Meta ma, mb;
+    layout_meta(A, &ma);
+    layout_meta(B, &mb);
+    BatchPlan bp;
+    if (plan_step_batched(c128, o.labels.data(), o.dims.data(),
+                          (int)o.labels.size(), ma, mb, batch_labels, nbatch,
+                          true, &bp, &bw->err) != TN_OK)
+      return;
+    bw->cls[s] = bp.cls;
+    bw->ws_bytes[s] = batch_step_ws(bp, esize);
+    bw->out[s] = o;
+    stored[i] = o;
+    alive[j] = 0;
+  }
+  bw->valid = true;
 }
 
 #endif  // TNC_STEP_PLAN_HPP

@@ -1354,6 +1354,91 @@ __global__ void k_splitk_reduce(const CT* __restrict__ ws,
   }
 }
 
+// Batched MFMA GEMM (TN_BATCH_GEMM): C[b] = A[b] @ B[b] for every batch
+// element in ONE launch, over packed [batch][M][K], [batch][K][N] ->
+// [batch][M][N]; no strides inside. Modelled on k_zgemm_mfma (same operand
+// and D-fragment maps through MfmaCore, same planar padded LDS image, same
+// bounds-guarded staging and store), with a 64x64 tile and four waves: the
+// scan above k_zgemm_mfma has 64x64 within 5% of 128x64 on big shapes; on the
+// small elements this class exists for (fewer than 256 tiles, often one) it
+// halves the row padding. Block = (element, tile): tile = blockIdx.x % tiles,
+// so a workgroup never straddles two elements. Ragged M, N and K are zero-
+// filled in staging (K needs no multiple of 4) and guarded in the store.
+#define BG_THREADS 256  // (BG_T: step_plan.hpp)
+template <typename CT>
+__global__ __launch_bounds__(BG_THREADS) void k_zgemm_batched(
+    const CT* __restrict__ A, const CT* __restrict__ B, CT* __restrict__ C,
+    u64 M, u64 N, u64 K, unsigned col_tiles, unsigned tiles) {
+  using RT = decltype(CT{}.x);
+  using Core = MfmaCore<RT>;
+  using acc_t = typename Core::acc_t;
+  __shared__ RT Ar[BG_T * A_LD];
+  __shared__ RT Ai[BG_T * A_LD];
+  __shared__ RT Br[MF_K * B_LD];
+  __shared__ RT Bi[MF_K * B_LD];
+
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  const unsigned elem = (unsigned)blockIdx.x / tiles;
+  const unsigned tile = (unsigned)blockIdx.x % tiles;
+  const u64 brow = (u64)(tile / col_tiles) * BG_T;
+  const u64 bcol = (u64)(tile % col_tiles) * BG_T;
+  A += (u64)elem * M * K;
+  B += (u64)elem * K * N;
+  C += (u64)elem * M * N;
+
+  acc_t cr[4], ci[4];
+  for (int f = 0; f < 4; ++f) {
+    cr[f] = acc_t{0, 0, 0, 0};
+    ci[f] = acc_t{0, 0, 0, 0};
+  }
+  const int fi = lane % 16;
+  const int fk = lane / 16;
+
+  for (u64 k0 = 0; k0 < K; k0 += MF_K) {
+    for (int i = threadIdx.x; i < BG_T * MF_K; i += BG_THREADS) {
+      int r = i / MF_K, c = i % MF_K;
+      CT v = (brow + r < M && k0 + c < K) ? A[(brow + r) * K + k0 + c]
+                                          : CT{0, 0};
+      Ar[r * A_LD + c] = v.x;
+      Ai[r * A_LD + c] = v.y;
+    }
+    for (int i = threadIdx.x; i < MF_K * BG_T; i += BG_THREADS) {
+      int r = i / BG_T, c = i % BG_T;
+      CT v = (k0 + r < K && bcol + c < N) ? B[(k0 + r) * N + bcol + c]
+                                          : CT{0, 0};
+      Br[r * B_LD + c] = v.x;
+      Bi[r * B_LD + c] = v.y;
+    }
+    __syncthreads();
+    for (int kq = 0; kq < MF_K / 4; ++kq) {
+      const int arow = wave * 16 + fi;
+      const int ak = kq * 4 + fk;
+      const RT ar = Ar[arow * A_LD + ak];
+      const RT ai = Ai[arow * A_LD + ak];
+      for (int f = 0; f < 4; ++f) {
+        const int bcolf = f * 16 + fi;
+        const RT br = Br[ak * B_LD + bcolf];
+        const RT bi = Bi[ak * B_LD + bcolf];
+        cr[f] = Core::mfma(ar, br, cr[f]);
+        cr[f] = Core::mfma(-ai, bi, cr[f]);
+        ci[f] = Core::mfma(ar, bi, ci[f]);
+        ci[f] = Core::mfma(ai, br, ci[f]);
+      }
+    }
+    __syncthreads();
+  }
+
+  const int ccol = lane % 16;
+  for (int f = 0; f < 4; ++f) {
+    for (int r = 0; r < 4; ++r) {
+      u64 row = brow + wave * 16 + Core::crow(lane, r);
+      u64 col = bcol + f * 16 + ccol;
+      if (row < M && col < N) C[row * N + col] = CT{cr[f][r], ci[f][r]};
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host-side planning
 // ---------------------------------------------------------------------------
@@ -1705,13 +1790,18 @@ static int run_dot(const Step<CT>& s) {
 
 // ---- smallk / anyk: small K, or skinny GEMM shapes; also where a TTGT step
 // goes when its workspace does not fit and the plan says gather_ok ----
+// `lead`: out axes ahead of the element's own (a batched step's batch axes,
+// which carry a stride in BOTH operands); nout counts them in
 template <typename CT>
-static int run_gather(const Step<CT>& s) {
+static int run_gather(const Step<CT>& s,
+                      const std::vector<AxisInfo>& lead = {}) {
   const StepPlan& p = s.p;
-  const u64 nout = p.nout(), K = p.k;
+  u64 nout = p.nout();
+  const u64 K = p.k;
   if (s.stats) s.stats->kind = 0;
   // out map: every out axis, with its source stride in A or B
-  std::vector<AxisInfo> oax;
+  std::vector<AxisInfo> oax(lead);
+  for (const AxisInfo& ax : lead) nout *= ax.dim;
   for (int i = 0; i < s.out_nd; ++i) {
     AxisInfo ax;
     ax.dim = s.out_shape[i];
@@ -1971,6 +2061,107 @@ static int einsum_dev_impl(const u64* out_labels, const u64* out_shape,
   return run_ttgt(s);
 }
 
+// ---- batch labels: plan_step_batched classifies, this dispatches ----
+
+// GEMM class: pack what is not [batch][M][K] / [batch][K][N] already, one
+// k_zgemm_batched launch, out permute when the caller's order is not
+// [batch][M legs][N legs]. TN_ERR_OOM when a buffer cannot be had.
+template <typename CT>
+static int run_batch_gemm(const BatchPlan& p, const u64* out_shape, int out_nd,
+                          const Meta& A, const Meta& B, CT* out,
+                          hipStream_t stream, WsCtx& ws, StepStats* stats) {
+  const StepPlan& e = p.ep;
+  const u64 M = e.m, N = e.n, K = e.k, nout = p.batch * M * N;
+  WsBlock<CT> tmpC(ws), packB(ws), packA(ws);
+  const CT* Ag = (const CT*)A.data;
+  const CT* Bg = (const CT*)B.data;
+  CT* Cg = out;
+  if (!e.direct) {
+    if (int rc = tmpC.alloc(nout * sizeof(CT))) return rc;
+    Cg = tmpC.p;
+  }
+  if (p.ws_pack_a) {
+    if (int rc = packA.alloc(p.ws_pack_a)) return rc;
+    if (int rc = launch_permute(
+            Ag, packA.p, p.batch * M * K,
+            batch_pack_axis_info(p, A, p.ba, p.Ae, e.a_axes), stream))
+      return rc;
+    Ag = packA.p;
+  }
+  if (p.ws_pack_b) {
+    if (int rc = packB.alloc(p.ws_pack_b)) return rc;
+    if (int rc = launch_permute(
+            Bg, packB.p, p.batch * K * N,
+            batch_pack_axis_info(p, B, p.bb, p.Be, e.b_axes), stream))
+      return rc;
+    Bg = packB.p;
+  }
+  const u64 tiles = p.row_tiles * p.col_tiles;
+  if (stats && stats->gemm_ev0)
+    HIP_CHECK(hipEventRecord(stats->gemm_ev0, stream));
+  k_zgemm_batched<<<dim3((unsigned)(p.batch * tiles)), BG_THREADS, 0,
+                    stream>>>(Ag, Bg, Cg, M, N, K, (unsigned)p.col_tiles,
+                              (unsigned)tiles);
+  if (stats && stats->gemm_ev1)
+    HIP_CHECK(hipEventRecord(stats->gemm_ev1, stream));
+  HIP_CHECK(hipGetLastError());
+  if (e.direct) return TN_OK;
+  return launch_permute((const CT*)tmpC.p, out, nout,
+                        batch_out_axis_info(p, out_shape, out_nd), stream);
+}
+
+template <typename CT>
+static int einsum_batched_impl(const u64* out_labels, const u64* out_shape,
+                               int out_nd, const Meta& A, const Meta& B,
+                               const u64* batch_labels, size_t nbatch,
+                               CT* out, hipStream_t stream, WsCtx& ws,
+                               StepStats* stats) {
+  BatchPlan bp;
+  std::string err;
+  if (int rc = plan_step_batched(std::is_same_v<CT, double2>, out_labels,
+                                 out_shape, out_nd, A, B, batch_labels, nbatch,
+                                 ws.stream2 != nullptr, &bp, &err)) {
+    g_last_error = err;
+    return rc;
+  }
+  const StepPlan& e = bp.ep;
+  if (stats) {
+    stats->m = e.m;
+    stats->n = e.n;
+    stats->k = e.k;
+    stats->kind = e.kind;
+  }
+  const u64* eshape = out_shape + bp.nb;
+  const int end = out_nd - bp.nb;
+  auto element = [&](u64 b) {
+    const CT* Ab = (const CT*)A.data + batch_offset(bp, A, bp.ba, b);
+    const CT* Bb = (const CT*)B.data + batch_offset(bp, B, bp.bb, b);
+    const Step<CT> s{e, eshape, end, bp.Ae, bp.Be, Ab, Bb,
+                     out + b * e.nout(), stream, ws, stats};
+    if (e.route == TN_ROUTE_DOT) return run_dot(s);
+    if (e.route == TN_ROUTE_GATHER) return run_gather(s);
+    return run_ttgt(s);
+  };
+  if (bp.cls == TN_BATCH_NONE) return element(0);
+  if (bp.cls == TN_BATCH_GATHER) {
+    std::vector<AxisInfo> lead;
+    for (int x = 0; x < bp.nb; ++x)
+      lead.push_back({bp.bdim[x], A.strides[bp.ba[x]], B.strides[bp.bb[x]]});
+    const Step<CT> s{e, eshape, end, bp.Ae, bp.Be, (const CT*)A.data,
+                     (const CT*)B.data, out, stream, ws, stats};
+    return run_gather(s, lead);
+  }
+  if (bp.cls == TN_BATCH_GEMM) {
+    int rc = run_batch_gemm(bp, out_shape, out_nd, A, B, out, stream, ws,
+                            stats);
+    // the batched buffers do not fit: LOOP needs 1/batch of the workspace
+    if (rc != TN_ERR_OOM) return rc;
+  }
+  for (u64 b = 0; b < bp.batch; ++b)
+    if (int rc = element(b)) return rc;
+  return TN_OK;
+}
+
 // ---------------------------------------------------------------------------
 // C API: device management + einsum entry points
 // ---------------------------------------------------------------------------
@@ -2012,6 +2203,12 @@ static int fill_meta(Meta* m, const u64* labels, const u64* shape,
   return TN_OK;
 }
 
+// the batch labels of the *_batched entry points (null: the plain einsum)
+struct BatchLabels {
+  const u64* labels;
+  size_t n;
+};
+
 template <typename CT>
 static int einsum_dev_entry(const u64* out_labels, const u64* out_shape,
                             size_t out_ndim, const u64* a_labels,
@@ -2019,7 +2216,8 @@ static int einsum_dev_entry(const u64* out_labels, const u64* out_shape,
                             const void* a_dev, size_t a_ndim,
                             const u64* b_labels, const u64* b_shape,
                             const i64* b_strides, const void* b_dev,
-                            size_t b_ndim, void* out_dev, void* stream) {
+                            size_t b_ndim, void* out_dev, void* stream,
+                            const BatchLabels* batch = nullptr) {
   int rc = require_gpu();
   if (rc) return rc;
   Meta A, B;
@@ -2028,6 +2226,10 @@ static int einsum_dev_entry(const u64* out_labels, const u64* out_shape,
   rc = fill_meta(&B, b_labels, b_shape, b_strides, b_dev, b_ndim);
   if (rc) return rc;
   WsCtx ws{nullptr, (hipStream_t)stream};
+  if (batch)
+    return einsum_batched_impl<CT>(out_labels, out_shape, (int)out_ndim, A, B,
+                                   batch->labels, batch->n, (CT*)out_dev,
+                                   (hipStream_t)stream, ws, nullptr);
   return einsum_dev_impl<CT>(out_labels, out_shape, (int)out_ndim, A, B,
                              (CT*)out_dev, (hipStream_t)stream, ws, nullptr);
 }
@@ -2154,7 +2356,8 @@ static int einsum_host_entry(const u64* out_labels, const u64* out_shape,
                              const void* a_data, size_t a_ndim,
                              const u64* b_labels, const u64* b_shape,
                              const i64* b_strides, const void* b_data,
-                             size_t b_ndim, void* out_data) {
+                             size_t b_ndim, void* out_data,
+                             const BatchLabels* batch = nullptr) {
   int rc = require_gpu();
   if (rc) return rc;
   HIP_CHECK(hipSetDevice(g_device));
@@ -2178,7 +2381,7 @@ static int einsum_host_entry(const u64* out_labels, const u64* out_shape,
   HIP_CHECK(hipMemcpy(db, b_data, b_span * es, hipMemcpyHostToDevice));
   rc = einsum_dev_entry<CT>(out_labels, out_shape, out_ndim, a_labels,
                             a_shape, a_strides, da, a_ndim, b_labels, b_shape,
-                            b_strides, db, b_ndim, dout, nullptr);
+                            b_strides, db, b_ndim, dout, nullptr, batch);
   if (rc == TN_OK) {
     HIP_CHECK(hipMemcpy(out_data, dout, out_elems * es,
                         hipMemcpyDeviceToHost));
@@ -2213,6 +2416,113 @@ extern "C" int tn_einsum_c64(const u64* out_labels, const u64* out_shape,
                                    a_shape, a_strides, a_data, a_ndim,
                                    b_labels, b_shape, b_strides, b_data,
                                    b_ndim, out_data);
+}
+
+// --- batch labels: C API ----------------------------------------------------
+
+#define TN_EINSUM_ARGS                                                       \
+  const u64 *out_labels, const u64 *out_shape, size_t out_ndim,              \
+      const u64 *a_labels, const u64 *a_shape, const i64 *a_strides,         \
+      const void *a_data, size_t a_ndim, const u64 *b_labels,                \
+      const u64 *b_shape, const i64 *b_strides, const void *b_data,          \
+      size_t b_ndim, const u64 *batch_labels, size_t nbatch
+#define TN_EINSUM_PASS                                                       \
+  out_labels, out_shape, out_ndim, a_labels, a_shape, a_strides, a_data,     \
+      a_ndim, b_labels, b_shape, b_strides, b_data, b_ndim
+
+extern "C" int tn_einsum_c128_batched(TN_EINSUM_ARGS, void* out_data) {
+  if (nbatch && !batch_labels) FAILV(TN_ERR_INVALID, "null batch labels");
+  const BatchLabels bl{batch_labels, nbatch};
+  return einsum_host_entry<double2>(TN_EINSUM_PASS, out_data, &bl);
+}
+
+extern "C" int tn_einsum_c64_batched(TN_EINSUM_ARGS, void* out_data) {
+  if (nbatch && !batch_labels) FAILV(TN_ERR_INVALID, "null batch labels");
+  const BatchLabels bl{batch_labels, nbatch};
+  return einsum_host_entry<float2>(TN_EINSUM_PASS, out_data, &bl);
+}
+
+extern "C" int tn_einsum_c128_batched_dev(TN_EINSUM_ARGS, void* out_dev,
+                                          void* stream) {
+  if (nbatch && !batch_labels) FAILV(TN_ERR_INVALID, "null batch labels");
+  const BatchLabels bl{batch_labels, nbatch};
+  return einsum_dev_entry<double2>(TN_EINSUM_PASS, out_dev, stream, &bl);
+}
+
+extern "C" int tn_einsum_c64_batched_dev(TN_EINSUM_ARGS, void* out_dev,
+                                         void* stream) {
+  if (nbatch && !batch_labels) FAILV(TN_ERR_INVALID, "null batch labels");
+  const BatchLabels bl{batch_labels, nbatch};
+  return einsum_dev_entry<float2>(TN_EINSUM_PASS, out_dev, stream, &bl);
+}
+
+// the plan einsum_batched_impl would act on; no GPU needed, none touched
+extern "C" int tn_plan_step_batched(int dtype, const u64* out_labels,
+                                    const u64* out_shape, size_t out_ndim,
+                                    const u64* a_labels, const u64* a_shape,
+                                    const i64* a_strides, size_t a_ndim,
+                                    const u64* b_labels, const u64* b_shape,
+                                    const i64* b_strides, size_t b_ndim,
+                                    const u64* batch_labels, size_t nbatch,
+                                    int has_stream2, tn_batch_plan* plan) {
+  if (!plan || (dtype != 0 && dtype != 1) || out_ndim > TN_MAXR ||
+      (nbatch && !batch_labels))
+    FAILV(TN_ERR_INVALID,
+          "null plan or batch labels, unknown dtype or rank over %d", TN_MAXR);
+  Meta A, B;
+  int rc = fill_meta(&A, a_labels, a_shape, a_strides, nullptr, a_ndim);
+  if (rc) return rc;
+  rc = fill_meta(&B, b_labels, b_shape, b_strides, nullptr, b_ndim);
+  if (rc) return rc;
+  BatchPlan p;
+  std::string err;
+  rc = plan_step_batched(dtype == 0, out_labels, out_shape, (int)out_ndim, A,
+                         B, batch_labels, nbatch, has_stream2 != 0, &p, &err);
+  if (rc) {
+    g_last_error = err;
+    return rc;
+  }
+  *plan = p;
+  return TN_OK;
+}
+
+static std::vector<LayoutTensor> layout_leaves(const u64* leaf_labels,
+                                               const u64* leaf_dims,
+                                               const u64* leaf_nd,
+                                               size_t nleaves) {
+  std::vector<LayoutTensor> lt(nleaves);
+  size_t at = 0;
+  for (size_t x = 0; x < nleaves; ++x) {
+    lt[x].labels.assign(leaf_labels + at, leaf_labels + at + leaf_nd[x]);
+    lt[x].dims.assign(leaf_dims + at, leaf_dims + at + leaf_nd[x]);
+    at += leaf_nd[x];
+  }
+  return lt;
+}
+
+extern "C" int tn_plan_batch_walk(int dtype, const u64* leaf_labels,
+                                  const u64* leaf_dims, const u64* leaf_nd,
+                                  size_t nleaves, const u64* pairs,
+                                  size_t nsteps, const u64* batch_labels,
+                                  size_t nbatch, int32_t* cls, u64* out_nd,
+                                  u64* out_labels, u64* ws_bytes) {
+  if ((dtype != 0 && dtype != 1) || (nleaves && !leaf_nd) ||
+      (nsteps && !pairs) || (nbatch && !batch_labels))
+    FAILV(TN_ERR_INVALID, "unknown dtype or null leaves/pairs/batch labels");
+  BatchWalkPlan bw;
+  plan_batch_walk(dtype == 0,
+                  layout_leaves(leaf_labels, leaf_dims, leaf_nd, nleaves),
+                  pairs, nsteps, batch_labels, nbatch, &bw);
+  if (!bw.valid) FAILV(TN_ERR_INVALID, "%s", bw.err.c_str());
+  for (size_t s = 0; s < nsteps; ++s) {
+    if (cls) cls[s] = bw.cls[s];
+    if (out_nd) out_nd[s] = bw.out[s].labels.size();
+    if (out_labels)
+      std::copy(bw.out[s].labels.begin(), bw.out[s].labels.end(),
+                out_labels + 64 * s);
+    if (ws_bytes) ws_bytes[s] = bw.ws_bytes[s];
+  }
+  return TN_OK;
 }
 
 // --- edge slicing (tn_net_contract_sliced) ---------------------------------
@@ -2387,7 +2697,15 @@ struct tn_net {
   // blocks are free for the other to take.
   SliceState* slices = nullptr;
 
+  // tn_net_contract_batched under a captured graph: the graph bakes the
+  // address of its final tensor, so that block stays reserved here while
+  // final_t holds the batched result; the next plain call takes it back
+  // (restore_graph_final) before it replays. Always an arena block.
+  DevTensor graph_final;
+
   void drop_graph() {
+    if (graph_final.data) arena.release(graph_final.data);
+    graph_final = DevTensor();
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     graph_exec = nullptr;
     graph_pairs.clear();
@@ -2589,6 +2907,10 @@ struct Walk {
   // times itself (tn_net_contract_sliced times the whole call)
   const bool timed;
   bool done = false;  // the final tensor was handed over
+  // tn_net_contract_batched: dispatch goes to einsum_batched_impl
+  bool batched = false;
+  const u64* batch_labels = nullptr;
+  size_t nbatch = 0;
 
   // `leaves`: the net's own, or a sliced run's shadow leaves in their place
   Walk(tn_net* n, CaptureLog* c, const std::vector<DevTensor>& leaves,
@@ -2748,6 +3070,10 @@ struct Walk {
     }
     int rc = with_dtype(net->dtype, [&](auto* t) {
       typedef std::remove_pointer_t<decltype(t)> CT;
+      if (batched)
+        return einsum_batched_impl<CT>(
+            out.labels.data(), out.dims.data(), (int)out.labels.size(), ma, mb,
+            batch_labels, nbatch, (CT*)out.data, net->stream, ws, &st);
       return einsum_dev_impl<CT>(out.labels.data(), out.dims.data(),
                                  (int)out.labels.size(), ma, mb, (CT*)out.data,
                                  net->stream, ws, &st);
@@ -2950,9 +3276,64 @@ static int contract_graph_capture(tn_net* net, const u64* pairs,
   return TN_OK;
 }
 
+// after tn_net_contract_batched: the captured graph's final block becomes
+// the net's final tensor again, as the replay expects to find it
+static void restore_graph_final(tn_net* net) {
+  if (!net->graph_final.data) return;
+  release_final(net);  // the batched result
+  net->final_t = std::move(net->graph_final);
+  net->graph_final = DevTensor();
+  net->final_in_arena = true;
+  net->has_final = true;
+}
+
+extern "C" int tn_net_contract_batched(tn_net* net, const u64* pairs,
+                                       size_t nsteps, const u64* batch_labels,
+                                       size_t nbatch, double* elapsed_ms) {
+  if (!net) FAILV(TN_ERR_INVALID, "null net");
+  if ((nsteps && !pairs) || (nbatch && !batch_labels))
+    FAILV(TN_ERR_INVALID, "null pairs or batch labels");
+  if (net->leaves.size() != nsteps + 1)
+    FAILV(TN_ERR_INVALID, "path did not fully contract the network");
+  HIP_CHECK(hipSetDevice(net->device));
+  BatchWalkPlan bw;
+  plan_batch_walk(
+      net->dtype == 0,
+      std::vector<LayoutTensor>(net->leaves.begin(), net->leaves.end()), pairs,
+      nsteps, batch_labels, nbatch, &bw);
+  if (!bw.valid) FAILV(TN_ERR_INVALID, "%s", bw.err.c_str());
+  if (net->slices) net->slices->drop_graph();  // its blocks are ours to take
+  // The plain walk's cached plan and captured graph stay. The graph's final
+  // block is set aside, reserved, so this walk's result lands elsewhere.
+  if (net->graph_state == 2 && !net->graph_final.data && net->has_final &&
+      net->final_t.owned && net->final_in_arena) {
+    net->graph_final = std::move(net->final_t);
+    net->final_t = DevTensor();
+    net->has_final = false;
+    net->final_in_arena = false;
+  } else {
+    release_final(net);
+  }
+  Walk w(net, nullptr, net->leaves);
+  w.batched = true;
+  w.batch_labels = batch_labels;
+  w.nbatch = nbatch;
+  if (int rc = w.begin(nsteps, false)) return rc;
+  for (size_t s = 0; s < nsteps; ++s) {
+    const u64 i = pairs[2 * s], j = pairs[2 * s + 1];
+    if (int rc = w.alloc_out(bw.out[s])) return rc;
+    if (int rc = w.dispatch(s, w.slots[i], w.slots[j], StepTimes()))
+      return rc;
+    w.retire(i, j);
+  }
+  if (int rc = w.read_times(nsteps, StepTimes(), elapsed_ms)) return rc;
+  return w.hand_over();
+}
+
 extern "C" int tn_net_contract(tn_net* net, const u64* pairs, size_t nsteps,
                                double* elapsed_ms) {
   if (!net) FAILV(TN_ERR_INVALID, "null net");
+  restore_graph_final(net);
   if (net->slices) net->slices->drop_graph();  // its blocks are ours to take
   if (net->graph_state == 2) {
     // a failed walk since capture clears final_t, whose address the replay
@@ -2980,6 +3361,7 @@ extern "C" int tn_net_contract_profiled(tn_net* net, const u64* pairs,
                                         double* gemm_ms, int32_t* kind,
                                         double* elapsed_ms) {
   if (!net) FAILV(TN_ERR_INVALID, "null net");
+  restore_graph_final(net);
   if (net->slices) net->slices->drop_graph();
   if (net->graph_state == 2 && !graph_pairs_match(net, pairs, nsteps))
     net->invalidate_graph();  // different path moves the final block

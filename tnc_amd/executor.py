@@ -19,10 +19,12 @@ from .tensor import CompositeTensor, LeafTensor
 
 class StepInfo:
     __slots__ = ("i", "j", "m", "n", "k", "flops", "out_legs", "out_dims",
-                 "packa", "packb", "pipe_p", "plan")
+                 "packa", "packb", "pipe_p", "plan", "ws", "batch")
 
     def __init__(self, i, j, m, n, k, flops, out_legs, out_dims,
                  packa=False, packb=False, pipe_p=0, plan=None):
+        self.ws = 0     # batched walk: workspace bytes of the step
+        self.batch = 1  # batched walk: the step batch
         self.i, self.j = i, j
         self.m, self.n, self.k = m, n, k
         self.flops = flops
@@ -88,6 +90,53 @@ def arena_bytes(leaves, steps, infos, esize=16, exact_dot=False):
     return int(peak * 1.15) + (1 << 20)
 
 
+def plan_steps_batched(leaves, steps, batch_edges, dtype="c128"):
+    """plan_steps for a batched walk (tn_net_contract_batched). Stored
+    orders, classes and workspaces come from tn_plan_batch_walk, the plan the
+    executor itself walks; each StepInfo carries the step's hiplib.BatchPlan
+    (`plan`, with `ws` the workspace bytes and `batch` the step batch), m/n/k
+    of ONE batch element and flops = element cost times the step batch.
+    Returns (infos, classes)."""
+    dims = {l: d for t in leaves for l, d in zip(t.legs, t.bond_dims)}
+    cls, out_labels, ws = hiplib.plan_batch_walk(
+        [(t.legs, t.bond_dims) for t in leaves], steps, batch_edges, dtype)
+    views = [LeafTensor(t.legs, t.bond_dims) for t in leaves]
+    infos = []
+    for s, (i, j) in enumerate(steps):
+        a, b = views[i], views[j]
+        out = LeafTensor(out_labels[s], [dims[l] for l in out_labels[s]])
+        bp = hiplib.plan_step_batched(out.legs, out.bond_dims, a.legs,
+                                      a.bond_dims, b.legs, b.bond_dims,
+                                      batch_edges, dtype=dtype,
+                                      has_stream2=True)
+        assert bp.cls == cls[s]
+        e = bp.elem
+        flops = ((e.k - 1.0) * 2.0 + e.k * 6.0) * e.m * e.n * bp.batch
+        info = StepInfo(i, j, e.m, e.n, e.k, flops, out.legs, out.bond_dims,
+                        packa=bool(e.pack_a), packb=bool(e.pack_b),
+                        pipe_p=e.pipe_p, plan=bp)
+        info.ws = ws[s]
+        info.batch = bp.batch
+        infos.append(info)
+        views[i] = out
+        views[j] = None
+    return infos, cls
+
+
+def batched_arena_bytes(infos, esize=16):
+    """Peak arena demand of a batched walk: live intermediates + the step's
+    output + the workspace tn_plan_batch_walk states for it, padded as
+    arena_bytes pads."""
+    live = {}
+    peak = 0
+    for info in infos:
+        out_b = info.batch * info.m * info.n * esize
+        peak = max(peak, sum(live.values()) + out_b + info.ws)
+        live.pop(info.j, None)
+        live[info.i] = out_b
+    return int(peak * 1.15) + (1 << 20)
+
+
 def reduced_leaves(leaves, slice_edges):
     """The leaves with the sliced legs removed (legs and dims only): what
     slicing.slice_network produces for any assignment."""
@@ -128,10 +177,13 @@ class ContractionEngine:
     `slice_edges` the engine is sized and planned for contract_sliced():
     infos and total_flops describe one slice, the arena holds one sliced
     walk, the accumulator and the shadow leaves; the leaves are uploaded
-    whole, once."""
+    whole, once. With `batch_edges` (labels shared by several leaves that
+    are kept, never summed) the engine is planned and sized for
+    contract_batched() by tn_plan_batch_walk, and the other contract calls
+    refuse."""
 
     def __init__(self, tn: CompositeTensor, replace_path: ContractionPath,
-                 device=0, dtype="c128", slice_edges=None):
+                 device=0, dtype="c128", slice_edges=None, batch_edges=None):
         if hiplib.device_count() == 0:
             raise RuntimeError("no AMD GPU present — tnc_amd has no CPU fallback")
         assert dtype in ("c128", "c64")
@@ -144,7 +196,14 @@ class ContractionEngine:
         self.final = final
         self.slice_edges = None if slice_edges is None else list(slice_edges)
         self.num_slices = 1
-        if self.slice_edges is None:
+        self.batch_edges = None if batch_edges is None else list(batch_edges)
+        if self.batch_edges is not None and self.slice_edges is not None:
+            raise ValueError("batch_edges cannot be combined with slice_edges")
+        if self.batch_edges is not None:
+            # refuses what the executor would refuse, before anything uploads
+            self.infos, self.batch_classes = plan_steps_batched(
+                leaves, steps, self.batch_edges, dtype)
+        elif self.slice_edges is None:
             self.infos = plan_steps(leaves, steps, dtype)
         else:
             # refuses what the executor would refuse, before anything uploads
@@ -159,7 +218,9 @@ class ContractionEngine:
         self.net = L.tn_net_create2(device, 0 if dtype == "c128" else 1)
         if not self.net:
             raise RuntimeError(f"tn_net_create failed: {hiplib.last_error()}")
-        if self.slice_edges is None:
+        if self.batch_edges is not None:
+            reserve = batched_arena_bytes(self.infos, self.esize)
+        elif self.slice_edges is None:
             reserve = arena_bytes(leaves, steps, self.infos, self.esize)
         else:
             reserve = sliced_arena_bytes(leaves, steps, self.slice_edges,
@@ -197,8 +258,31 @@ class ContractionEngine:
                 raise RuntimeError(f"tn_net_add_leaf failed: {hiplib.last_error()}")
         self._pairs = hiplib._u64arr([x for p in steps for x in p])
 
+    def _refuse_batched(self, what):
+        if self.batch_edges is not None:
+            raise RuntimeError(
+                f"{what} on an engine built with batch_edges; use "
+                "contract_batched()")
+
+    def contract_batched(self) -> float:
+        """One batched contraction (tn_net_contract_batched): the final
+        tensor keeps the batch edges. Returns device wall ms."""
+        if self.batch_edges is None:
+            raise RuntimeError("engine was built without batch_edges")
+        ms = ctypes.c_double()
+        hiplib.check(
+            hiplib.lib().tn_net_contract_batched(
+                self.net, self._pairs, len(self.steps),
+                hiplib._u64arr(self.batch_edges), len(self.batch_edges),
+                ctypes.byref(ms)
+            ),
+            "tn_net_contract_batched",
+        )
+        return ms.value
+
     def contract(self) -> float:
         """One full contraction; returns device wall ms."""
+        self._refuse_batched("contract()")
         ms = ctypes.c_double()
         hiplib.check(
             hiplib.lib().tn_net_contract(
@@ -215,6 +299,7 @@ class ContractionEngine:
         assignment indices, first edge most significant: index t is
         list(slicing.iter_assignments(tn, slice_edges))[t]. Returns the
         device ms of all assignments."""
+        self._refuse_batched("contract_sliced()")
         if self.slice_edges is None:
             raise RuntimeError("engine was built without slice_edges")
         if which is None:
@@ -234,6 +319,7 @@ class ContractionEngine:
     def contract_profiled(self):
         """Contraction with per-step HIP-event timings.
         Returns (elapsed_ms, step_ms[], gemm_ms[], kind[])."""
+        self._refuse_batched("contract_profiled()")
         n = len(self.steps)
         step_ms = (ctypes.c_double * n)()
         gemm_ms = (ctypes.c_double * n)()
@@ -292,3 +378,28 @@ def contract_tensor_network_gpu(tn: CompositeTensor, replace_path, device=0):
         return eng.result()
     finally:
         eng.close()
+
+
+def amplitudes_gpu(tn: CompositeTensor, replace_path, batch_edge, device=0,
+                   dtype="c128"):
+    """All amplitudes of a Circuit.into_amplitudes_network network in one
+    batched walk. Returns (legs, ndarray) with batch_edge first: row r is
+    what contract_tensor_network_gpu gives for bitstring r's own network. A
+    stored order with the batch edge elsewhere is transposed on the host.
+    When no leaf carries batch_edge (every bitstring the same on every
+    closed qubit) nothing is batched and the result has no batch axis."""
+    carried = any(batch_edge in t.legs
+                  for t in flatten_network(tn, replace_path)[0])
+    eng = ContractionEngine(tn, replace_path, device, dtype,
+                            batch_edges=[batch_edge] if carried else [])
+    try:
+        eng.contract_batched()
+        legs, data = eng.result()
+    finally:
+        eng.close()
+    if batch_edge in legs and legs[0] != batch_edge:
+        at = legs.index(batch_edge)
+        order = [at] + [x for x in range(len(legs)) if x != at]
+        legs = [legs[x] for x in order]
+        data = np.ascontiguousarray(np.transpose(data, order))
+    return legs, data

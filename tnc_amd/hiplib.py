@@ -119,6 +119,37 @@ def lib() -> ctypes.CDLL:
             ctypes.c_void_p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
             u64p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double),
         ]
+        L.tn_plan_step_batched.restype = ctypes.c_int
+        L.tn_plan_step_batched.argtypes = [
+            ctypes.c_int, u64p, u64p, ctypes.c_size_t,
+            u64p, u64p, i64p, ctypes.c_size_t,
+            u64p, u64p, i64p, ctypes.c_size_t,
+            u64p, ctypes.c_size_t,
+            ctypes.c_int, ctypes.POINTER(BatchPlan),
+        ]
+        L.tn_plan_batch_walk.restype = ctypes.c_int
+        L.tn_plan_batch_walk.argtypes = [
+            ctypes.c_int, u64p, u64p, u64p, ctypes.c_size_t,
+            u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_int32), u64p, u64p, u64p,
+        ]
+        for name in ("tn_einsum_c128_batched", "tn_einsum_c64_batched"):
+            fn = getattr(L, name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = (L.tn_einsum_c128.argtypes[:-1]
+                           + [u64p, ctypes.c_size_t, ctypes.c_void_p])
+        for name in ("tn_einsum_c128_batched_dev",
+                     "tn_einsum_c64_batched_dev"):
+            fn = getattr(L, name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = (L.tn_einsum_c128_dev.argtypes[:-2]
+                           + [u64p, ctypes.c_size_t, ctypes.c_void_p,
+                              ctypes.c_void_p])
+        L.tn_net_contract_batched.restype = ctypes.c_int
+        L.tn_net_contract_batched.argtypes = [
+            ctypes.c_void_p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_double),
+        ]
         _lib = L
     return _lib
 
@@ -174,6 +205,66 @@ def plan_step(out_labels, out_shape, a_labels, a_shape, b_labels, b_shape,
     )
     check(rc, "tn_plan_step")
     return plan
+
+
+class BatchPlan(ctypes.Structure):
+    """tn_batch_plan (include/tnc_hip.h): how one batched step is run."""
+
+    _fields_ = [
+        ("batch", ctypes.c_uint64), ("cls", ctypes.c_int32),
+        ("dispatches", ctypes.c_uint64),
+        ("ws_pack_a", ctypes.c_uint64), ("ws_pack_b", ctypes.c_uint64),
+        ("elem", StepPlan),
+    ]
+
+
+BATCH_NONE, BATCH_GATHER, BATCH_GEMM, BATCH_LOOP = range(4)
+
+
+def plan_step_batched(out_labels, out_shape, a_labels, a_shape, b_labels,
+                      b_shape, batch_labels, dtype="c128", has_stream2=False,
+                      a_strides=None, b_strides=None) -> BatchPlan:
+    """The plan of one batched einsum step (tn_plan_step_batched): plan_step
+    plus the labels that are kept, not summed, when both operands carry
+    them. Needs no GPU."""
+    plan = BatchPlan()
+    rc = lib().tn_plan_step_batched(
+        {"c128": 0, "c64": 1}[dtype],
+        _u64arr(out_labels), _u64arr(out_shape), len(out_labels),
+        _u64arr(a_labels), _u64arr(a_shape),
+        None if a_strides is None else _i64arr(a_strides), len(a_labels),
+        _u64arr(b_labels), _u64arr(b_shape),
+        None if b_strides is None else _i64arr(b_strides), len(b_labels),
+        _u64arr(batch_labels), len(batch_labels),
+        int(has_stream2), ctypes.byref(plan),
+    )
+    check(rc, "tn_plan_step_batched")
+    return plan
+
+
+def plan_batch_walk(leaves, steps, batch_labels, dtype="c128"):
+    """The walk plan of tn_net_contract_batched (tn_plan_batch_walk). leaves
+    and steps as for plan_layouts. Returns (cls[], out_labels[], ws_bytes[]),
+    one entry per step: the TN_BATCH_* class, the labels of the step's output
+    in stored order, and the workspace the step asks for beyond its output.
+    Raises on a refused plan. Needs no GPU."""
+    n = len(steps)
+    cls = (ctypes.c_int32 * n)()
+    nd = (ctypes.c_uint64 * n)()
+    labels = (ctypes.c_uint64 * max(64 * n, 1))()
+    ws = (ctypes.c_uint64 * n)()
+    rc = lib().tn_plan_batch_walk(
+        {"c128": 0, "c64": 1}[dtype],
+        _u64arr([l for labs, _ in leaves for l in labs]),
+        _u64arr([d for _, dims in leaves for d in dims]),
+        _u64arr([len(labs) for labs, _ in leaves]), len(leaves),
+        _u64arr([x for p in steps for x in p]), n,
+        _u64arr(batch_labels), len(batch_labels), cls, nd, labels, ws,
+    )
+    check(rc, "tn_plan_batch_walk")
+    return (list(cls),
+            [[labels[64 * s + x] for x in range(nd[s])] for s in range(n)],
+            list(ws))
 
 
 def plan_layouts(leaves, steps, dtype="c128"):
@@ -243,7 +334,9 @@ def _i64arr(vals):
 
 
 def _einsum_host(out_labels, a_labels, a, b_labels, b, out_shape, npdtype,
-                 esize, fn_name):
+                 esize, fn_name, batch_labels=None):
+    """batch_labels None: the plain entry point; a list (possibly empty): the
+    *_batched one, which takes the labels ahead of the out buffer."""
     a = np.asarray(a, dtype=npdtype)
     b = np.asarray(b, dtype=npdtype)
     if out_shape is None:
@@ -256,16 +349,38 @@ def _einsum_host(out_labels, a_labels, a, b_labels, b, out_shape, npdtype,
     out = np.empty(tuple(out_shape), dtype=npdtype)
     a_str = [s // esize for s in a.strides]
     b_str = [s // esize for s in b.strides]
+    batch = ([] if batch_labels is None
+             else [_u64arr(batch_labels), len(batch_labels)])
     rc = getattr(lib(), fn_name)(
         _u64arr(out_labels), _u64arr(out_shape), len(out_labels),
         _u64arr(a_labels), _u64arr(a.shape), _i64arr(a_str),
         a.ctypes.data_as(ctypes.c_void_p), a.ndim,
         _u64arr(b_labels), _u64arr(b.shape), _i64arr(b_str),
         b.ctypes.data_as(ctypes.c_void_p), b.ndim,
-        out.ctypes.data_as(ctypes.c_void_p),
+        *batch, out.ctypes.data_as(ctypes.c_void_p),
     )
     check(rc, fn_name)
     return out
+
+
+def einsum_batched_c128(out_labels, a_labels, a: np.ndarray, b_labels,
+                        b: np.ndarray, batch_labels,
+                        out_shape=None) -> np.ndarray:
+    """einsum_c128 with batch labels (tn_einsum_c128_batched): a label of
+    batch_labels carried by both operands is kept in out, not summed, and
+    those labels lead out_labels. Accepts non-contiguous views."""
+    return _einsum_host(out_labels, a_labels, a, b_labels, b, out_shape,
+                        np.complex128, 16, "tn_einsum_c128_batched",
+                        list(batch_labels))
+
+
+def einsum_batched_c64(out_labels, a_labels, a: np.ndarray, b_labels,
+                       b: np.ndarray, batch_labels,
+                       out_shape=None) -> np.ndarray:
+    """complex64 batched einsum (tn_einsum_c64_batched)."""
+    return _einsum_host(out_labels, a_labels, a, b_labels, b, out_shape,
+                        np.complex64, 8, "tn_einsum_c64_batched",
+                        list(batch_labels))
 
 
 def einsum_c128(out_labels, a_labels, a: np.ndarray, b_labels, b: np.ndarray,
