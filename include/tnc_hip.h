@@ -101,6 +101,19 @@ enum {
   TN_GEMM_C128_GATHER = 5, /* c128 MFMA reading through the pack permute */
   TN_GEMM_C64_PURE = 6,    /* c64 MFMA, pure shapes */
 };
+/* The gather-route kernels. P2 / TBL: every axis of the out map and of the K
+ * map is a power of two, indices decode by shift and mask; otherwise by
+ * division and remainder. */
+enum {
+  TN_GK_NONE = 0,
+  TN_GK_SMALLK = 1,     /* k_einsum_smallk<false>: K <= 64, offsets in LDS */
+  TN_GK_SMALLK_P2 = 2,  /* k_einsum_smallk<true> */
+  TN_GK_SMALLK_TBL = 3, /* k_einsum_smallk_tbl: 2^26 <= out elements < 2^32,
+                         * rank >= 8, four 8-bit offset tables, grid capped
+                         * at 32768 blocks */
+  TN_GK_ANYK = 4,       /* k_einsum_anyk<false>: K > 64 */
+  TN_GK_ANYK_P2 = 5,    /* k_einsum_anyk<true> */
+};
 
 /* How one einsum step is dispatched: everything that follows from dtype,
  * shapes, strides and the TN_* environment switches alone. What depends on
@@ -143,6 +156,12 @@ typedef struct tn_step_plan {
    * when pipe_p == 0; pipe_perm_b is 0 when B is ready). */
   int32_t perm_a, perm_b, perm_out;
   int32_t pipe_perm_a, pipe_perm_b;
+  /* the gather kernel (TN_GK_*) and its grid, in blocks of 256 threads:
+   * what the step launches on the gather route, and what a TTGT step with
+   * gather_ok launches when it drops there on out-of-memory. TN_GK_NONE and
+   * 0 on the dot route and on TTGT steps without gather_ok. */
+  int32_t gather_kernel;
+  int32_t gather_blocks;
 } tn_step_plan;
 
 /* Plan the step tn_einsum_*_dev would run on these operands (dtype 0 =
@@ -211,6 +230,11 @@ typedef struct tn_batch_plan {
   uint64_t dispatches;  /* compute dispatches: 1 for GATHER/GEMM, batch for LOOP */
   uint64_t ws_pack_a, ws_pack_b; /* batched pack buffers (GEMM class), 0 if ready */
   tn_step_plan elem;    /* plan of one batch element (whole step when NONE) */
+  /* class GATHER: the kernel (TN_GK_*) of the one launch over all of out,
+   * the batch axes counted into its out map (a batch dim that is no power of
+   * two makes it a div/mod kernel whatever elem.gather_kernel says). 0 for
+   * the other classes. */
+  int32_t gather_kernel;
 } tn_batch_plan;
 
 /* Plan the step tn_einsum_*_batched_dev would run. Arguments as tn_plan_step

@@ -6,8 +6,13 @@ runs the case on the GPU, so a case cannot drift to another kernel unnoticed.
 
 A case is a dict:
   name            case id
-  group           "gemm" | "packs" | "tperm" | "pipe" | "dot"
+  group           "gemm" | "packs" | "tperm" | "pipe" | "dot" | "gather"
   a, b            [(label, dim), ...] in stored (row-major) order
+  a_strides       optional: element strides of A, a view into a larger buffer
+                  of a_base elements starting at element a_offset
+  big             optional flag: more than 2^25 output elements. Runs once,
+                  through the host entry, with integer operands, compared
+                  bit for bit
   out             out labels
   dtypes          the dtypes the case runs in
   env             environment the plan depends on ({} = default switches)
@@ -15,11 +20,22 @@ A case is a dict:
                   False: through the einsum entry points (has_stream2 = False)
   plan            expected tn_step_plan fields; a (c128, c64) tuple where the
                   dtypes differ. route / kernel / dot_form are names of the
-                  hiplib constants (ROUTE_*, GEMM_*, DOT_*).
+                  hiplib constants (ROUTE_*, GEMM_*, DOT_*, GK_*).
   select          tperm only: which operand is the 0/1 selection matrix
                   ("a" or "b"); the other one is random
 
 Labels: M legs 1.., K legs 101.., N legs 200 / 201...
+
+Grid-stride second passes. grid_for caps a grid at 64 * 2048 blocks of 256
+threads = 2^25 threads (the table kernel at 32768 blocks = 2^23), so a loop
+`for (p = ...; p < nout; p += gridDim.x * blockDim.x)` takes a second pass
+only past 2^25 elements. The big cases do that for k_einsum_smallk<false>
+(G_pass2_np2), k_einsum_smallk<true> (G_pass2_p2), k_einsum_smallk_tbl
+(G_tbl, 8 passes) and k_permute_ct<false> (R_unpack_pass2). Two loops of the
+same shape stay on their first pass in this suite: k_einsum_anyk, because a
+K > 64 operand at that nout is several GB, and k_splitk_reduce, because
+split-K needs fewer than 192 tiles and nout then stays below 2^21. No test
+of this table takes those two further.
 """
 
 M0, K0, N0 = 1, 101, 201
@@ -181,9 +197,107 @@ DOT_CASES = [
     _dot("D_tiled", _legs(K0, 20),
          dict(k=1 << 20, kind=6, dot_form="DOT_TILED", tbits=8,
               dot_blocks=256)),
+    # linear form, the first K past the gather route: one block, 65 of its
+    # 256 threads live
+    _dot("D_linear65", [(K0, 65)],
+         dict(k=65, kind=5, dot_form="DOT_LINEAR", tbits=0, dot_blocks=1)),
+    # linear form at the block cap: every block takes a second pass, the
+    # tail of 77 is partial
+    _dot("D_linear_stride", [(K0, 256 * 2048 + 77)],
+         dict(k=256 * 2048 + 77, kind=5, dot_form="DOT_LINEAR", tbits=0,
+              dot_blocks=2048)),
 ]
 
-CASES = GEMM_CASES + [R_PACKS] + TPERM_CASES + [P_SUBBOX] + DOT_CASES
+# ---- gather route: k_einsum_smallk<*>, k_einsum_smallk_tbl, k_einsum_anyk<*>
+# gather_kernel is what run_gather launches; gather_blocks its grid.
+
+
+def _gather(name, a, b, out, m, n, k, kernel, blocks, dtypes=("c128", "c64"),
+            **extra):
+    return dict(name=name, group="gather", dtypes=dtypes, env={},
+                engine=False, a=a, b=b, out=out,
+                plan=dict(NO_PERM, route="ROUTE_GATHER", kind=0, m=m, n=n,
+                          k=k, gather_kernel=kernel, gather_blocks=blocks),
+                **extra)
+
+
+# a rank-8 qubit state with the gate's two qubits at positions 3 and 5
+_Q8 = _legs(M0, 3) + [(K0, 2)] + [(M0 + 3, 2)] + [(K0 + 1, 2)] + _legs(5, 2)
+_GATE = [(N0, 2), (N0 + 1, 2), (K0, 2), (K0 + 1, 2)]
+# 26 qubits, the gate's at positions 3 and 17
+_Q26 = (_legs(M0, 3) + [(K0, 2)] + _legs(4, 13) + [(K0 + 1, 2)]
+        + _legs(17, 8))
+# the 26 out legs, shuffled once (numpy default_rng(26).permutation)
+_Q26_OUT = [15, 21, 2, 4, 6, 10, 7, 202, 8, 11, 22, 16, 13, 19, 24, 9, 1, 201,
+            3, 14, 17, 20, 23, 12, 18, 5]
+
+GATHER_CASES = [
+    # div/mod decode
+    _gather("G_np2", [(1, 3), (2, 5), (101, 7)], [(101, 7), (201, 4)],
+            [1, 2, 201], 15, 4, 7, "GK_SMALLK", 1),
+    # the rqc36 workhorse: a two-qubit gate applied in place. The out map
+    # has 8 axes, but nout is far below the table kernel's 2^26
+    _gather("G_gate", _Q8, _GATE, [1, 2, 3, 201, 4, 202, 5, 6], 64, 4, 4,
+            "GK_SMALLK_P2", 1),
+    # the same, an out permute folded into the map (default_rng(8))
+    _gather("G_gate_outorder", _Q8, _GATE, [4, 202, 1, 6, 201, 2, 3, 5],
+            64, 4, 4, "GK_SMALLK_P2", 1),
+    # K = TN_SMALLK: all 64 LDS offset slots
+    _gather("G_k64", [(1, 8), (101, 64)], [(101, 64), (201, 300)], [1, 201],
+            8, 300, 64, "GK_SMALLK", 10),
+    # neither skinny nor GEMM-worthy
+    _gather("G_k64_mid", [(1, 100), (101, 64)], [(101, 64), (201, 50)],
+            [1, 201], 100, 50, 64, "GK_SMALLK", 20),
+    # the first K past the LDS table
+    _gather("G_k65", [(1, 8), (101, 65)], [(101, 65), (201, 300)], [1, 201],
+            8, 300, 65, "GK_ANYK", 10),
+    # two K axes, B's in the other order
+    _gather("G_k65_np2", [(1, 3), (101, 5), (102, 13)],
+            [(102, 13), (101, 5), (201, 301)], [1, 201], 3, 301, 65,
+            "GK_ANYK", 4),
+    _gather("G_anyk_p2", [(1, 4), (101, 1024)], [(101, 1024), (201, 4096)],
+            [1, 201], 4, 4096, 1024, "GK_ANYK_P2", 64),
+    # rank-1 A: no A-only out axis
+    _gather("G_m1", [(101, 64)], [(101, 64), (201, 1000)], [201],
+            1, 1000, 64, "GK_SMALLK", 4),
+    # nout = 1, empty out map. One more K element and the step is a dot:
+    # D_linear65
+    _gather("G_scalar64", [(101, 64)], [(101, 64)], [], 1, 1, 64,
+            "GK_SMALLK_P2", 1),
+    # K = 1, empty K map
+    _gather("G_outer", [(1, 5)], [(201, 6)], [1, 201], 5, 6, 1, "GK_SMALLK",
+            1),
+    # A = rows 0, 2, 4 and columns 1..2 of a [6, 4] buffer: source strides
+    # that are not suffix products
+    _gather("G_strided", [(1, 3), (101, 2)], [(101, 2), (201, 5)], [1, 201],
+            3, 5, 2, "GK_SMALLK", 1, a_strides=(8, 1), a_offset=1,
+            a_base=24),
+    # the table kernel: 2^26 output elements over 26 axes, 8 passes of its
+    # capped grid, bits 24-25 of the index go to table 3
+    _gather("G_tbl", _Q26, _GATE, _Q26_OUT, 1 << 24, 4, 4, "GK_SMALLK_TBL",
+            32768, big=True),
+    # nout = 33 648 691 > 2^25: second pass of the div/mod variant
+    _gather("G_pass2_np2", [(1, 8209)], [(201, 4099)], [1, 201], 8209, 4099,
+            1, "GK_SMALLK", 131072, dtypes=("c64",), big=True),
+    # nout = 2^26 but only 2 axes: second pass of the shift/mask variant,
+    # not the table
+    _gather("G_pass2_p2", [(1, 8192)], [(201, 8192)], [1, 201], 8192, 8192,
+            1, "GK_SMALLK_P2", 131072, dtypes=("c64",), big=True),
+]
+
+# the unpack of a 33.6 M element GEMM result through k_permute_ct<false>:
+# second pass of its grid-stride loop
+R_UNPACK_PASS2 = dict(
+    name="R_unpack_pass2", group="packs", dtypes=("c64",), env={},
+    engine=False, big=True,
+    a=[(1, 8209), (101, 16)], b=[(101, 16), (201, 4099)], out=[201, 1],
+    plan=dict(NO_PERM, route="ROUTE_TTGT", kind=3, kernel="GEMM_MFMA",
+              m=8209, k=16, n=4099, splitk=1, kchunk=16, pack_a=0, pack_b=0,
+              perm_out=1, gather_kernel="GK_SMALLK", gather_blocks=131072,
+              dot_form="DOT_LINEAR"))
+
+CASES = (GEMM_CASES + [R_PACKS, R_UNPACK_PASS2] + TPERM_CASES + [P_SUBBOX]
+         + DOT_CASES + GATHER_CASES)
 
 # every (case, dtype) pair, for pytest.mark.parametrize
 PAIRS = [(c, d) for c in CASES for d in c["dtypes"]]
@@ -200,6 +314,21 @@ def plan_args(case):
     return [list(case["out"]), [dims[l] for l in case["out"]],
             [l for l, _ in case["a"]], [d for _, d in case["a"]],
             [l for l, _ in case["b"]], [d for _, d in case["b"]]]
+
+
+def plan_kwargs(case):
+    """Keyword arguments of hiplib.plan_step the case adds (its strides)."""
+    if "a_strides" in case:
+        return {"a_strides": list(case["a_strides"])}
+    return {}
+
+
+def nout_of(case):
+    dims = dict(case["a"] + case["b"])
+    n = 1
+    for l in case["out"]:
+        n *= dims[l]
+    return n
 
 
 def expected_plan(case, dtype):

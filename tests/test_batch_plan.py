@@ -46,6 +46,36 @@ def test_gather_class():
     assert p.elem.route == H.ROUTE_GATHER
     assert (p.elem.m, p.elem.n, p.elem.k) == (2, 2, 2)
     assert p.ws_pack_a == 0 and p.ws_pack_b == 0
+    # the batch axis of 3 leads the launch's out map: div/mod, whatever the
+    # pow2 element alone would take
+    assert p.gather_kernel == H.GK_SMALLK
+    assert p.elem.gather_kernel == H.GK_SMALLK_P2
+
+
+def test_gather_class_kernel():
+    """The batch-level gather kernel counts the batch axes in; the other
+    classes report none."""
+    from tnc_amd import hiplib as H
+
+    p = plan(*mm(2, 2, 2, beta=4), [BETA])
+    assert (p.cls, p.batch) == (H.BATCH_GATHER, 4)
+    assert p.gather_kernel == p.elem.gather_kernel == H.GK_SMALLK_P2
+    # K past the LDS table, skinny element
+    p = plan(*mm(2, 2, 128, beta=4), [BETA])
+    assert (p.cls, p.gather_kernel) == (H.BATCH_GATHER, H.GK_ANYK_P2)
+    p = plan(*mm(2, 2, 128, beta=3), [BETA])
+    assert (p.gather_kernel, p.elem.gather_kernel) == (H.GK_ANYK,
+                                                       H.GK_ANYK_P2)
+    # no batch label, GEMM and LOOP classes: no batch-level launch
+    p = plan([(I_, 2), (J_, 2)], [(I_, 2), (K_, 2)], [(K_, 2), (J_, 2)],
+             [BETA])
+    assert (p.cls, p.gather_kernel) == (H.BATCH_NONE, H.GK_NONE)
+    assert p.elem.gather_kernel == H.GK_SMALLK_P2
+    p = plan(*mm(40, 40, 72), [BETA])
+    assert (p.cls, p.gather_kernel) == (H.BATCH_GEMM, H.GK_NONE)
+    p = plan([(BETA, 3)], [(BETA, 3), (K_, 128)], [(BETA, 3), (K_, 128)],
+             [BETA])
+    assert (p.cls, p.gather_kernel) == (H.BATCH_LOOP, H.GK_NONE)
 
 
 @pytest.mark.parametrize("dtype,esize", [("c128", 16), ("c64", 8)])

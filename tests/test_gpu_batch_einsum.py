@@ -80,6 +80,23 @@ def test_gather_gate_apply(dtype):
     p, _ = run_case(dtype, H.BATCH_GATHER, [BETA, 1, 2], [BETA, 1, 3], a,
                     [BETA, 3, 2], b, [BETA])
     assert p.dispatches == 1
+    # batch 3 leads the out map: the one launch is the div/mod kernel, though
+    # an element alone would take the shift/mask one
+    assert p.gather_kernel == H.GK_SMALLK
+    assert p.elem.gather_kernel == H.GK_SMALLK_P2
+
+
+@pytest.mark.parametrize("dtype", ["c128", "c64"])
+def test_gather_gate_apply_batch4(dtype):
+    """A pow2 batch keeps the launch on the shift/mask kernel."""
+    from tnc_amd import hiplib as H
+
+    a, b = rand((4, 2, 2), 9, dtype), rand((4, 2, 2), 10, dtype)
+    p, _ = run_case(dtype, H.BATCH_GATHER, [BETA, 1, 2], [BETA, 1, 3], a,
+                    [BETA, 3, 2], b, [BETA])
+    assert p.dispatches == 1 and p.batch == 4
+    assert p.gather_kernel == H.GK_SMALLK_P2
+    assert p.elem.gather_kernel == H.GK_SMALLK_P2
 
 
 @pytest.mark.parametrize("dtype", ["c128", "c64"])
@@ -90,6 +107,7 @@ def test_gather_outer_product(dtype):
     p, _ = run_case(dtype, H.BATCH_GATHER, [BETA, 1, 2], [BETA, 1], a,
                     [BETA, 2], b, [BETA])
     assert p.elem.k == 1
+    assert p.gather_kernel == H.GK_SMALLK
 
 
 @pytest.mark.parametrize("dtype", ["c128", "c64"])
@@ -98,8 +116,9 @@ def test_gather_nonpow2_and_out_order(dtype):
 
     a, b = rand((3, 3, 5), 5, dtype), rand((5, 3, 6), 6, dtype)
     # beta in the middle of B; out keeps the N leg ahead of the M leg
-    run_case(dtype, H.BATCH_GATHER, [BETA, 2, 1], [BETA, 1, 3], a,
-             [3, BETA, 2], b, [BETA])
+    p, _ = run_case(dtype, H.BATCH_GATHER, [BETA, 2, 1], [BETA, 1, 3], a,
+                    [3, BETA, 2], b, [BETA])
+    assert p.gather_kernel == H.GK_SMALLK
 
 
 @pytest.mark.parametrize("dtype", ["c128", "c64"])
@@ -110,8 +129,9 @@ def test_gather_strided_view(dtype):
     a = base[:, ::2, 1:3]  # [3, 3, 2], element strides (24, 8, 1)
     assert not a.flags["C_CONTIGUOUS"]
     b = rand((3, 2, 5), 8, dtype)
-    run_case(dtype, H.BATCH_GATHER, [BETA, 1, 2], [BETA, 1, 3], a,
-             [BETA, 3, 2], b, [BETA])
+    p, _ = run_case(dtype, H.BATCH_GATHER, [BETA, 1, 2], [BETA, 1, 3], a,
+                    [BETA, 3, 2], b, [BETA])
+    assert p.gather_kernel == H.GK_SMALLK
 
 
 # ---- GEMM class ------------------------------------------------------------

@@ -6,6 +6,14 @@ and the unpack (caller-chosen out order) through k_permute_ct, strided
 views, pow2 and non-pow2 dims. The VALU GEMM k_zgemm_v1 and the tiled
 permute k_permute_tile are not reached by any shape here: their cases, each
 with the plan it must get, are in test_gpu_kernel_reach.py.
+
+The smallk / anyk / outer-product tests here check values only: which of the
+five gather kernels a shape launches (k_einsum_smallk<false|true>,
+k_einsum_smallk_tbl, k_einsum_anyk<false|true>) is the plan's gather_kernel,
+and the cases that pin each variant to a named shape (K = 64 and 65, nout =
+1, K = 1, strided A, the table kernel, the second pass of the grid-stride
+loops), bit for bit on integers and under guard bands, are the gather group
+of tests/kernel_reach_cases.py, run by test_gpu_kernel_reach.py.
 """
 
 import numpy as np

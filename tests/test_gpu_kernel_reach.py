@@ -14,8 +14,17 @@ instead of silently moving it to another kernel. What the table reaches:
   k_permute_tile          pack of A, pack of B, unpack, pipeline
                           window with a source gap                     c128 c64
   pack pipeline           ready-B window branch (P_subbox)             c128 c64
+  k_permute_ct<false>     second grid-stride pass (R_unpack_pass2)     c64
   k_dot_partial<*>        gather form, pow2 and not                    c128 c64
   k_dot_tile              tiled form                                   c128 c64
+  k_dot_partial_linear    one block of 65; 2048 blocks, second pass    c128 c64
+  k_einsum_smallk<false>  div/mod maps, K = 64, K = 1, rank-1 A,
+                          strided A                                    c128 c64
+                          second grid-stride pass (G_pass2_np2)        c64
+  k_einsum_smallk<true>   gate apply, folded out permute, nout = 1     c128 c64
+                          second grid-stride pass (G_pass2_p2)         c64
+  k_einsum_smallk_tbl     2^26 elements, 8 passes (G_tbl)              c128 c64
+  k_einsum_anyk<*>        K = 65, two K axes, pow2                     c128 c64
 
 Comparison. The tiled-permute cases contract a random operand with a 0/1
 selection matrix: the einsum is a permutation composed with a column (row)
@@ -33,14 +42,29 @@ inputs rounded first, then widened) and S the oracle contraction of |A| and
 misplaced product is of order 1; the bound at the largest non-exact K is
 about 1e-2 in c64 (rag_split, K 271) and 1e-9 in c128 (P_subbox, K 512).
 
-Guard bands. The GEMM-edge cases and R_packs run through
+The gather cases run twice. Once with integer operands, real and imaginary
+parts drawn from -4..4: every product and partial sum is an integer of
+magnitude at most 32 K <= 2^15 (K <= 1024), far below 2^24, so the result is
+exact in c64 and c128 in any summation order, with or without fma, and must
+equal the oracle contraction of the same integers (computed in c128, cast)
+bit for bit: a dropped, duplicated or misaddressed element cannot hide in a
+tolerance. And once with N(0,1) operands against the bound above, which
+integers alone would not hold an accumulator of the wrong width to. The big
+cases (more than 2^25 output elements, T.big) run the integer way only,
+through the host entry, against np.multiply.outer (K = 1) or np.tensordot
+plus transpose.
+
+Guard bands. The GEMM-edge cases, R_packs and the gather cases that are not
+big run through
 tn_einsum_c128_dev / tn_einsum_c64_dev over torch buffers laid out as
 [256 guard | out | 256 guard] elements, the guards (and out) pre-filled with
 a fixed NaN bit pattern, A and B each followed by 256 NaN elements. After
 the call the guards must be bit-identical and the result free of NaN: a
 store past either end of out, a read past the end of an operand that reaches
 the result, or an element never stored all fail. With correct kernels every
-access stays inside the operands.
+access stays inside the operands. G_strided hands the device entry its
+strides and a pointer one element into its [6, 4] base buffer; the guard
+follows the whole base.
 """
 
 import ctypes
@@ -84,9 +108,33 @@ def rand(shape, rng, dtype):
     return x.astype(NPDT[dtype])
 
 
+def ints(shape, rng, dtype):
+    """Integer-valued complex: real and imaginary parts from -4..4, drawn as
+    int8 (a 2^26-element operand is not generated through float64)."""
+    x = np.empty(shape, dtype=NPDT[dtype])
+    x.real = rng.integers(-4, 5, size=shape, dtype=np.int8)
+    x.imag = rng.integers(-4, 5, size=shape, dtype=np.int8)
+    return x
+
+
 def rng_of(case, dtype):
     return np.random.default_rng(zlib.crc32(
         ("%s-%s" % (case["name"], dtype)).encode()))
+
+
+def operands(case, dtype, draw):
+    """(a, b, a_base) drawn by rand or ints from the case's seed. a_base is
+    None, or for a strided case the flat buffer that `a` is a view into."""
+    rng = rng_of(case, dtype)
+    if "a_strides" in case:
+        a_base = draw([case["a_base"]], rng, dtype)
+        esize = a_base.itemsize
+        a = np.lib.stride_tricks.as_strided(
+            a_base[case["a_offset"]:], shape=dims(case["a"]),
+            strides=[s * esize for s in case["a_strides"]], writeable=False)
+    else:
+        a_base, a = None, draw(dims(case["a"]), rng, dtype)
+    return a, draw(dims(case["b"]), rng, dtype), a_base
 
 
 def assert_plan(case, dtype):
@@ -96,7 +144,7 @@ def assert_plan(case, dtype):
     assert not case["env"]
     assert not [k for k in ENV_SWITCHES if os.environ.get(k)]
     p = hiplib.plan_step(*T.plan_args(case), dtype=dtype,
-                         has_stream2=case["engine"])
+                         has_stream2=case["engine"], **T.plan_kwargs(case))
     assert T.plan_mismatches(case, dtype, p, hiplib) == []
     assert p.kernel != hiplib.GEMM_C128_3M
 
@@ -120,10 +168,22 @@ def error_ratio(case, dtype, got, a, b):
     return float(np.max(np.abs(got.astype(np.complex128) - ref) / bound))
 
 
+def exact_mismatches(case, dtype, got, a, b):
+    """Number of elements that differ from the oracle contraction of the
+    (integer-valued) operands, computed in c128 and cast."""
+    ref = oracle.contract_ndarrays(
+        case["out"], labels(case["a"]), a.astype(np.complex128),
+        labels(case["b"]), b.astype(np.complex128)).astype(NPDT[dtype])
+    got = np.asarray(got)
+    assert got.shape == np.shape(ref) and got.dtype == NPDT[dtype]
+    return int(np.count_nonzero(got != ref))
+
+
 def report(case, dtype, what):
     p = T.expected_plan(case, dtype)
-    print("REACH %s %s %s %s" % (case["name"], dtype,
-                                 p.get("kernel", p["dot_form"]), what))
+    kernel = (p["gather_kernel"] if case["group"] == "gather"
+              else p.get("kernel") or p["dot_form"])
+    print("REACH %s %s %s %s" % (case["name"], dtype, kernel, what))
 
 
 # ---- runners ---------------------------------------------------------------
@@ -135,9 +195,10 @@ def run_host(case, dtype, a, b):
     return fn(case["out"], labels(case["a"]), a, labels(case["b"]), b)
 
 
-def run_dev_guarded(case, dtype, a, b):
+def run_dev_guarded(case, dtype, a, b, a_base=None):
     """The device entry over torch buffers with guard bands (module
-    docstring). Returns the result; asserts the guards and NaN-freeness."""
+    docstring). Returns the result; asserts the guards and NaN-freeness.
+    a_base: the flat buffer a strided `a` views (operands)."""
     import torch
 
     from tnc_amd import hiplib
@@ -155,15 +216,19 @@ def run_dev_guarded(case, dtype, a, b):
         flat = np.concatenate([np.ascontiguousarray(x).reshape(-1), tail])
         return torch.from_numpy(flat.view(real)).cuda()
 
-    a_dev, b_dev = operand(a), operand(b)
+    a_dev, b_dev = operand(a if a_base is None else a_base), operand(b)
+    a_ptr, a_strides = a_dev.data_ptr(), None
+    if a_base is not None:
+        a_ptr += case["a_offset"] * esize
+        a_strides = hiplib._i64arr(case["a_strides"])
     buf = torch.full(((GUARD + nout + GUARD) * words,), PATTERN,
                      dtype=torch.int64, device="cuda")
     u64, vp = hiplib._u64arr, ctypes.c_void_p
     fn = L.tn_einsum_c128_dev if dtype == "c128" else L.tn_einsum_c64_dev
     torch.cuda.synchronize()
     rc = fn(u64(case["out"]), u64(out_shape), len(out_shape),
-            u64(labels(case["a"])), u64(dims(case["a"])), None,
-            vp(a_dev.data_ptr()), len(case["a"]),
+            u64(labels(case["a"])), u64(dims(case["a"])), a_strides,
+            vp(a_ptr), len(case["a"]),
             u64(labels(case["b"])), u64(dims(case["b"])), None,
             vp(b_dev.data_ptr()), len(case["b"]),
             vp(buf.data_ptr() + GUARD * esize), None)
@@ -186,7 +251,10 @@ def run_dev_guarded(case, dtype, a, b):
 # guarded cases run in one child that imports torch first. The child runs
 # every case and prints one record each; the tests below assert on them.
 
-BOUNDED = [(c, d) for c, d in T.PAIRS if c["group"] in ("gemm", "packs")]
+BOUNDED = [(c, d) for c, d in T.PAIRS
+           if c["group"] in ("gemm", "packs", "gather") and not c.get("big")]
+GEMM_EDGES = [(c, d) for c, d in BOUNDED if c["group"] != "gather"]
+GATHER = [(c, d) for c, d in BOUNDED if c["group"] == "gather"]
 
 GUARD_CHILD = r"""
 import json, sys
@@ -204,10 +272,12 @@ for cid in sys.argv[2:]:
     rec = {"id": cid}
     try:
         R.assert_plan(case, dtype)
-        rng = R.rng_of(case, dtype)
-        a = R.rand(R.dims(case["a"]), rng, dtype)
-        b = R.rand(R.dims(case["b"]), rng, dtype)
-        got = R.run_dev_guarded(case, dtype, a, b)
+        if case["group"] == "gather":
+            a, b, a_base = R.operands(case, dtype, R.ints)
+            got = R.run_dev_guarded(case, dtype, a, b, a_base)
+            rec["mismatches"] = R.exact_mismatches(case, dtype, got, a, b)
+        a, b, a_base = R.operands(case, dtype, R.rand)
+        got = R.run_dev_guarded(case, dtype, a, b, a_base)
         rec["ratio"] = R.error_ratio(case, dtype, got, a, b)
     except AssertionError as e:
         rec["error"] = "AssertionError: %s" % e
@@ -235,8 +305,8 @@ def guarded_records():
     return proc, recs
 
 
-@pytest.mark.parametrize("case,dtype", BOUNDED,
-                         ids=["%s-%s" % (c["name"], d) for c, d in BOUNDED])
+@pytest.mark.parametrize("case,dtype", GEMM_EDGES,
+                         ids=["%s-%s" % (c["name"], d) for c, d in GEMM_EDGES])
 def test_gemm_edges_guarded(case, dtype, guarded_records):
     assert_plan(case, dtype)
     proc, recs = guarded_records
@@ -246,6 +316,59 @@ def test_gemm_edges_guarded(case, dtype, guarded_records):
     assert "error" not in rec, rec["error"]
     report(case, dtype, "worst |err|/bound = %.3g" % rec["ratio"])
     assert rec["ratio"] <= 1.0
+
+
+# ---- gather route: guard bands, exact on integers, derived bound -----------
+
+@pytest.mark.parametrize("case,dtype", GATHER,
+                         ids=["%s-%s" % (c["name"], d) for c, d in GATHER])
+def test_gather_guarded(case, dtype, guarded_records):
+    assert_plan(case, dtype)
+    proc, recs = guarded_records
+    rec = recs.get("%s-%s" % (case["name"], dtype))
+    assert rec is not None, ("case did not run", proc.returncode,
+                             proc.stdout[-2000:], proc.stderr[-2000:])
+    assert "error" not in rec, rec["error"]
+    report(case, dtype, "integer mismatches = %d, worst |err|/bound = %.3g"
+           % (rec["mismatches"], rec["ratio"]))
+    assert rec["mismatches"] == 0
+    assert rec["ratio"] <= 1.0
+
+
+BIG = [(c, d) for c, d in T.PAIRS if c.get("big")]
+
+
+def big_reference(case, a, b):
+    """The contraction by numpy alone, in the operands' own dtype (exact on
+    these integers): outer product when nothing is contracted, else
+    tensordot; then the out order by transpose."""
+    al, bl = labels(case["a"]), labels(case["b"])
+    shared = [l for l in al if l in bl]
+    if shared:
+        c = np.tensordot(a, b, axes=([al.index(l) for l in shared],
+                                     [bl.index(l) for l in shared]))
+    else:
+        c = np.multiply.outer(a, b)
+    c_legs = ([l for l in al if l not in shared]
+              + [l for l in bl if l not in shared])
+    return np.transpose(c, [c_legs.index(l) for l in case["out"]])
+
+
+@pytest.mark.parametrize("case,dtype", BIG,
+                         ids=["%s-%s" % (c["name"], d) for c, d in BIG])
+def test_second_pass_exact(case, dtype):
+    """More than 2^25 output elements: the grid-stride loop of the case's
+    kernel takes a second pass (G_tbl: eight). Integer operands, host entry,
+    bit for bit."""
+    assert_plan(case, dtype)
+    assert T.nout_of(case) > 1 << 25
+    a, b, _ = operands(case, dtype, ints)
+    got = run_host(case, dtype, a, b)
+    ref = big_reference(case, a, b)
+    assert got.dtype == NPDT[dtype] and got.shape == ref.shape
+    bad = int(np.count_nonzero(got != ref))
+    report(case, dtype, "integer mismatches = %d of %d" % (bad, got.size))
+    assert bad == 0
 
 
 # ---- tiled permute: exact ---------------------------------------------------
@@ -317,9 +440,7 @@ DOTS = [(c, d) for c, d in T.PAIRS if c["group"] == "dot"]
                          ids=["%s-%s" % (c["name"], d) for c, d in DOTS])
 def test_dot_forms(case, dtype):
     assert_plan(case, dtype)
-    rng = rng_of(case, dtype)
-    a = rand(dims(case["a"]), rng, dtype)
-    b = rand(dims(case["b"]), rng, dtype)
+    a, b, _ = operands(case, dtype, rand)
     got = run_host(case, dtype, a, b)
     ratio = error_ratio(case, dtype, got, a, b)
     report(case, dtype, "worst |err|/bound = %.3g" % ratio)
@@ -390,6 +511,7 @@ def test_pipeline_window_subbox(case, dtype):
 
 def test_every_case_runs():
     """No case of the table is left without a test above."""
-    ran = BOUNDED + TPERM + DOTS + PIPE
+    ran = GEMM_EDGES + GATHER + BIG + TPERM + DOTS + PIPE
+    assert len(ran) == len(T.PAIRS)
     assert sorted(T.PAIR_IDS) == sorted("%s-%s" % (c["name"], d)
                                         for c, d in ran)

@@ -6,6 +6,10 @@ sanitizers and run (no GPU, nothing loaded into Python):
   slice_plan_check   slice plan
   tile_perm_check    address replay of k_permute_tile and k_dot_tile, with
                      self-tests that fail when a plan entry is perturbed
+  gather_map_check   both encodings of the gather maps against a mixed-radix
+                     loop, the four offset tables of k_einsum_smallk_tbl,
+                     plan_gather_kernel at its thresholds, with self-tests
+                     that fail when a shift, mask or table entry is perturbed
 
 Each is one translation unit with its own main that includes only
 step_plan.hpp. Where the sanitizer runtime cannot be linked the same file is
@@ -54,7 +58,8 @@ def run(exe, env_extra=None):
      "layout_plan_check OK (scatter off)"),
     ("slice_plan_check", {}, "slice_plan_check OK"),
     ("tile_perm_check", {}, "tile_perm_check OK"),
-], ids=["layout", "layout_scatter_off", "slice", "tile_perm"])
+    ("gather_map_check", {}, "gather_map_check OK"),
+], ids=["layout", "layout_scatter_off", "slice", "tile_perm", "gather_map"])
 def test_native_check(name, env, ok_line, tmp_path):
     proc = run(build(name, tmp_path), env)
     assert proc.returncode == 0, (proc.stdout, proc.stderr)

@@ -102,6 +102,34 @@ def test_gather_route(m, k, n):
     p = mm(m, k, n)
     assert (p.route, p.kind) == (H.ROUTE_GATHER, 0)
     assert p.ws_pack_a == p.ws_pack_b == p.ws_tmp_c == p.ws_split == 0
+    assert p.gather_kernel == (H.GK_SMALLK_P2 if k <= 64 else H.GK_ANYK_P2)
+    assert p.gather_blocks == 1
+
+
+def test_gather_kernel_only_where_run_gather_can_run():
+    """gather_kernel / gather_blocks are set on the gather route and on TTGT
+    steps with gather_ok (the out-of-memory fallback), 0 elsewhere."""
+    from tnc_amd import hiplib as H
+
+    # dot route
+    p = plan([], [(K_, 128)], [(K_, 128)])
+    assert p.route == H.ROUTE_DOT
+    assert (p.gather_kernel, p.gather_blocks) == (H.GK_NONE, 0)
+    # TTGT, K > 64 and not skinny: no fallback
+    p = mm(16, 128, 16)
+    assert p.route == H.ROUTE_TTGT and not p.gather_ok
+    assert (p.gather_kernel, p.gather_blocks) == (H.GK_NONE, 0)
+    # TTGT with gather_ok: K <= 64 ...
+    p = mm(128, 16, 64)
+    assert p.route == H.ROUTE_TTGT and p.gather_ok
+    assert (p.gather_kernel, p.gather_blocks) == (H.GK_SMALLK_P2, 32)
+    p = mm(129, 64, 65)
+    assert p.route == H.ROUTE_TTGT and p.gather_ok
+    assert (p.gather_kernel, p.gather_blocks) == (H.GK_SMALLK, 33)
+    # ... the grid is capped at 64 * 2048 blocks
+    p = mm(1 << 14, 16, 1 << 12)
+    assert p.route == H.ROUTE_TTGT and p.gather_ok
+    assert (p.gather_kernel, p.gather_blocks) == (H.GK_SMALLK_P2, 1 << 17)
 
 
 def test_ttgt_v1():

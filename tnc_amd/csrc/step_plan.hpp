@@ -4,8 +4,9 @@
 // a StepPlan: route (dot / gather / TTGT), which operands get packed, the
 // pack-pipeline windows, split-K, the GEMM kernel, the permute kernel of
 // every pack and unpack (plan_permute_tile: k_permute_tile or k_permute_ct,
-// over the axis lists the executor launches with) and the workspace the step
-// will ask for. No HIP call, no HIP header: it builds with a plain host
+// over the axis lists the executor launches with), the gather kernel and its
+// grid (plan_gather_kernel, likewise) and the workspace the step will ask
+// for. No HIP call, no HIP header: it builds with a plain host
 // compiler and runs without a GPU. The executor (einsum_dev_impl), the walk
 // plan of a whole path (plan_layouts, below: stored orders and look-ahead
 // packs) and the Python arena model (through tn_plan_step) all read this
@@ -123,6 +124,61 @@ struct AxisList {
   const int* end() const { return v + n; }
 };
 
+// ---- gather maps ----------------------------------------------------------
+// A packed row-major index p over an axis list (outer..inner) decodes to one
+// coordinate per axis; the source offsets are the sums of coordinate times
+// stride. Two ENCODINGS of the decode, chosen per launch:
+//   div/mod     c_i = (p / pstride[i]) % dim[i]   pstride = suffix product
+//   shift/mask  c_i = (p >> pstride[i]) & dim[i]  pstride = log2 of it,
+//               (every dim a power of two)        dim = dim - 1
+struct GatherMap {
+  int n;
+  int pow2;             // if set: pstride holds shifts, dim holds masks
+  u64 pstride[TN_MAXR]; // packed-linear stride (suffix product) or shift
+  u64 dim[TN_MAXR];     // axis dim, or mask (dim-1) when pow2
+  i64 sa[TN_MAXR];      // source-A stride in elements (0 if absent)
+  i64 sb[TN_MAXR];      // source-B stride in elements
+};
+
+inline int log2_u64(u64 v) {
+  int s = 0;
+  while ((1ull << s) < v) ++s;
+  return s;
+}
+
+inline bool axes_pow2(const std::vector<AxisInfo>& axes) {
+  for (const auto& a : axes)
+    if (a.dim & (a.dim - 1)) return false;
+  return true;
+}
+
+// Encode a map. The pow2 (shift/mask) and general (div/mod) ENCODINGS are
+// incompatible; when a kernel takes several maps the caller must pick ONE
+// encoding for all of them (allow_pow2 = the joint decision).
+inline int build_map(const std::vector<AxisInfo>& axes, GatherMap* m,
+                     bool allow_pow2 = true) {
+  int n = (int)axes.size();
+  if (n > TN_MAXR) return -1;
+  m->n = n;
+  u64 pstride = 1;
+  bool p2 = allow_pow2 && axes_pow2(axes);
+  for (int i = n - 1; i >= 0; --i) {
+    m->pstride[i] = pstride;
+    m->dim[i] = axes[i].dim;
+    m->sa[i] = axes[i].sa;
+    m->sb[i] = axes[i].sb;
+    pstride *= axes[i].dim;
+  }
+  m->pow2 = p2 ? 1 : 0;
+  if (p2) {
+    for (int i = 0; i < n; ++i) {
+      m->pstride[i] = (u64)log2_u64(m->pstride[i]);
+      m->dim[i] = m->dim[i] - 1;
+    }
+  }
+  return 0;
+}
+
 // ---- environment switches, each read once on first use --------------------
 //   TN_NO_PIPELINE    set: never use the pack pipeline
 //   TN_PIPELINE_FORCE set: pipeline every shape-feasible step, profitability
@@ -200,6 +256,76 @@ inline int grid_for(u64 nout, int block = 256) {
   if (blocks > cap) blocks = cap;
   if (blocks == 0) blocks = 1;
   return (int)blocks;
+}
+
+// The axis lists of a gather launch. plan_step (gather_kernel) and run_gather
+// (the launch) both build them here.
+// Out map: `lead` (a batched step's batch axes, which carry a stride in BOTH
+// operands), then every out axis with its source stride in A or B.
+inline std::vector<AxisInfo> gather_out_axis_info(
+    const StepPlan& p, const u64* out_shape, int out_nd, const Meta& A,
+    const Meta& B, const std::vector<AxisInfo>& lead = {}) {
+  std::vector<AxisInfo> oax;
+  oax.reserve(lead.size() + out_nd);
+  oax.assign(lead.begin(), lead.end());
+  for (int i = 0; i < out_nd; ++i) {
+    AxisInfo ax;
+    ax.dim = out_shape[i];
+    ax.sa = p.apos[i] >= 0 ? A.strides[p.apos[i]] : 0;
+    ax.sb = p.bpos[i] >= 0 ? B.strides[p.bpos[i]] : 0;
+    oax.push_back(ax);
+  }
+  return oax;
+}
+
+// K axes with their strides in A and B
+inline std::vector<AxisInfo> k_axis_info(const StepPlan& p, const Meta& A,
+                                         const Meta& B) {
+  std::vector<AxisInfo> kax;
+  kax.reserve(p.k_a.n + 1);
+  for (int t = 0; t < p.k_a.n; ++t)
+    kax.push_back(
+        {A.dims[p.k_a[t]], A.strides[p.k_a[t]], B.strides[p.k_b[t]]});
+  return kax;
+}
+
+// K map of a gather launch: never empty (K = 1 decodes one axis of 1)
+inline std::vector<AxisInfo> gather_k_axis_info(const StepPlan& p,
+                                                const Meta& A, const Meta& B) {
+  std::vector<AxisInfo> kax = k_axis_info(p, A, B);
+  if (kax.empty()) kax.push_back({1, 0, 0});
+  return kax;
+}
+
+// Which gather kernel run_gather launches (TN_GK_*), on how many blocks of
+// 256 threads, and the one encoding both maps take. pow2 only when EVERY axis
+// of both maps is a power of two. K <= TN_SMALLK: the K offsets sit in LDS
+// (k_einsum_smallk), past it they are decoded per k (k_einsum_anyk). The
+// table decode (k_einsum_smallk_tbl) pays once ~4 offsets/thread are
+// amortized over >= 8 elements and the per-element decode is actually deep;
+// its index is 32-bit.
+struct GatherChoice {
+  int kernel;  // TN_GK_*
+  int blocks;
+  bool pow2;
+};
+
+inline GatherChoice plan_gather_kernel(const std::vector<AxisInfo>& oax,
+                                       const std::vector<AxisInfo>& kax,
+                                       u64 nout, u64 K) {
+  GatherChoice c;
+  c.pow2 = axes_pow2(oax) && axes_pow2(kax);
+  c.blocks = grid_for(nout);
+  if (K > TN_SMALLK) {
+    c.kernel = c.pow2 ? TN_GK_ANYK_P2 : TN_GK_ANYK;
+  } else if (c.pow2 && nout >= (1ull << 26) && nout < (1ull << 32) &&
+             oax.size() >= 8) {
+    c.kernel = TN_GK_SMALLK_TBL;
+    if (c.blocks > 32768) c.blocks = 32768;
+  } else {
+    c.kernel = c.pow2 ? TN_GK_SMALLK_P2 : TN_GK_SMALLK;
+  }
+  return c;
 }
 
 // Tiled bit-permutation dot: both operands are contiguous pow2 spans of the
@@ -631,6 +757,15 @@ inline int plan_step(bool c128, const u64* out_labels, const u64* out_shape,
   const bool skinny = (M < 16 || N < 16);
   const bool gemm_worthy = (K >= 16 && M >= MF_T && N >= MF_TN);
   p.gather_ok = (K <= TN_SMALLK || skinny);
+  if (p.gather_ok) {
+    // the kernel run_gather would launch: this step's own on the gather
+    // route, the out-of-memory fallback's on the TTGT route
+    const GatherChoice gc = plan_gather_kernel(
+        gather_out_axis_info(p, out_shape, out_nd, A, B),
+        gather_k_axis_info(p, A, B), nout, K);
+    p.gather_kernel = gc.kernel;
+    p.gather_blocks = gc.blocks;
+  }
   if (p.gather_ok && !gemm_worthy) {
     p.route = TN_ROUTE_GATHER;
     p.kind = 0;
@@ -1161,6 +1296,16 @@ inline std::vector<AxisInfo> batch_out_axis_info(const BatchPlan& p,
   return ax;
 }
 
+// Batch axes of a GATHER-class launch, ahead of the element's out axes
+inline std::vector<AxisInfo> batch_lead_axis_info(const BatchPlan& p,
+                                                  const Meta& A,
+                                                  const Meta& B) {
+  std::vector<AxisInfo> lead;
+  for (int x = 0; x < p.nb; ++x)
+    lead.push_back({p.bdim[x], A.strides[p.ba[x]], B.strides[p.bb[x]]});
+  return lead;
+}
+
 inline bool axis_info_ready(const std::vector<AxisInfo>& ax) {
   i64 stride = 1;
   for (int i = (int)ax.size() - 1; i >= 0; --i) {
@@ -1249,6 +1394,13 @@ inline int plan_step_batched(bool c128, const u64* out_labels,
   const u64 tiles = p.row_tiles * p.col_tiles;
   if (e.route == TN_ROUTE_GATHER) {
     p.cls = TN_BATCH_GATHER;
+    // one launch over all of out: the batch axes lead the out map
+    p.gather_kernel =
+        plan_gather_kernel(
+            gather_out_axis_info(e, out_shape + p.nb, out_nd - p.nb, p.Ae,
+                                 p.Be, batch_lead_axis_info(p, A, B)),
+            gather_k_axis_info(e, p.Ae, p.Be), p.batch * e.nout(), e.k)
+            .kernel;
   } else if (e.route == TN_ROUTE_TTGT && e.splitk == 1 &&
              e.row_tiles * e.col_tiles < TN_BATCH_MAXTILES &&
              tiles < (1ull << 31) / p.batch &&  // the grid is 32-bit

@@ -59,17 +59,8 @@ extern "C" const char* tn_last_error(void) { return g_last_error.c_str(); }
   } while (0)
 
 // ---------------------------------------------------------------------------
-// gather maps
+// gather maps (GatherMap, build_map: step_plan.hpp)
 // ---------------------------------------------------------------------------
-
-struct GatherMap {
-  int n;
-  int pow2;             // if set: pstride holds shifts, dim holds masks
-  u64 pstride[TN_MAXR]; // packed-linear stride (suffix product) or shift
-  u64 dim[TN_MAXR];     // axis dim, or mask (dim-1) when pow2
-  i64 sa[TN_MAXR];      // source-A stride in elements (0 if absent)
-  i64 sb[TN_MAXR];      // source-B stride in elements
-};
 
 template <bool P2>
 __device__ __forceinline__ void gather2(const GatherMap& m, u64 p, i64& oa,
@@ -1443,45 +1434,6 @@ __global__ __launch_bounds__(BG_THREADS) void k_zgemm_batched(
 // host-side planning
 // ---------------------------------------------------------------------------
 
-static int log2_u64(u64 v) {
-  int s = 0;
-  while ((1ull << s) < v) ++s;
-  return s;
-}
-
-static bool axes_pow2(const std::vector<AxisInfo>& axes) {
-  for (const auto& a : axes)
-    if (a.dim & (a.dim - 1)) return false;
-  return true;
-}
-
-// Encode a map. The pow2 (shift/mask) and general (div/mod) ENCODINGS are
-// incompatible; when a kernel takes several maps the caller must pick ONE
-// encoding for all of them (allow_pow2 = the joint decision).
-static int build_map(const std::vector<AxisInfo>& axes, GatherMap* m,
-                     bool allow_pow2 = true) {
-  int n = (int)axes.size();
-  if (n > TN_MAXR) return -1;
-  m->n = n;
-  u64 pstride = 1;
-  bool p2 = allow_pow2 && axes_pow2(axes);
-  for (int i = n - 1; i >= 0; --i) {
-    m->pstride[i] = pstride;
-    m->dim[i] = axes[i].dim;
-    m->sa[i] = axes[i].sa;
-    m->sb[i] = axes[i].sb;
-    pstride *= axes[i].dim;
-  }
-  m->pow2 = p2 ? 1 : 0;
-  if (p2) {
-    for (int i = 0; i < n; ++i) {
-      m->pstride[i] = (u64)log2_u64(m->pstride[i]);
-      m->dim[i] = m->dim[i] - 1;
-    }
-  }
-  return 0;
-}
-
 static void ensure_mempool(int device) {
   static bool done[64] = {};
   if (device >= 0 && device < 64 && !done[device]) {
@@ -1743,16 +1695,6 @@ struct PipeEvents {
   }
 };
 
-// K axes with their strides in A and B
-static std::vector<AxisInfo> k_axis_info(const StepPlan& p, const Meta& A,
-                                         const Meta& B) {
-  std::vector<AxisInfo> kax;
-  for (int t = 0; t < p.k_a.n; ++t)
-    kax.push_back(
-        {A.dims[p.k_a[t]], A.strides[p.k_a[t]], B.strides[p.k_b[t]]});
-  return kax;
-}
-
 // ---- dot: scalar output, large K ----
 template <typename CT>
 static int run_dot(const Step<CT>& s) {
@@ -1799,43 +1741,37 @@ static int run_gather(const Step<CT>& s,
   u64 nout = p.nout();
   const u64 K = p.k;
   if (s.stats) s.stats->kind = 0;
-  // out map: every out axis, with its source stride in A or B
-  std::vector<AxisInfo> oax(lead);
   for (const AxisInfo& ax : lead) nout *= ax.dim;
-  for (int i = 0; i < s.out_nd; ++i) {
-    AxisInfo ax;
-    ax.dim = s.out_shape[i];
-    ax.sa = p.apos[i] >= 0 ? s.A.strides[p.apos[i]] : 0;
-    ax.sb = p.bpos[i] >= 0 ? s.B.strides[p.bpos[i]] : 0;
-    oax.push_back(ax);
-  }
-  std::vector<AxisInfo> kax = k_axis_info(p, s.A, s.B);
-  if (kax.empty()) kax.push_back({1, 0, 0});
-  bool p2 = axes_pow2(oax) && axes_pow2(kax);
+  const std::vector<AxisInfo> oax =
+      gather_out_axis_info(p, s.out_shape, s.out_nd, s.A, s.B, lead);
+  const std::vector<AxisInfo> kax = gather_k_axis_info(p, s.A, s.B);
+  // the kernel, the grid and the maps' encoding: plan_gather_kernel
+  const GatherChoice gc = plan_gather_kernel(oax, kax, nout, K);
   GatherMap omap, kmap;
-  if (build_map(oax, &omap, p2) || build_map(kax, &kmap, p2))
+  if (build_map(oax, &omap, gc.pow2) || build_map(kax, &kmap, gc.pow2))
     FAILV(TN_ERR_INVALID, "rank too large");
-  int blocks = grid_for(nout);
-  if (K <= TN_SMALLK) {
-    // table decode pays once ~4 offsets/thread are amortized over >=8
-    // elements and the per-element decode is actually deep
-    if (p2 && nout >= (1ull << 26) && nout < (1ull << 32) && omap.n >= 8)
-      k_einsum_smallk_tbl<<<blocks > 32768 ? 32768 : blocks, 256, 0,
-                            s.stream>>>(s.Adata, s.Bdata, s.out, nout, omap,
-                                        kmap, (int)K);
-    else if (p2)
+  const int blocks = gc.blocks;
+  switch (gc.kernel) {
+    case TN_GK_SMALLK_TBL:
+      k_einsum_smallk_tbl<<<blocks, 256, 0, s.stream>>>(
+          s.Adata, s.Bdata, s.out, nout, omap, kmap, (int)K);
+      break;
+    case TN_GK_SMALLK_P2:
       k_einsum_smallk<true><<<blocks, 256, 0, s.stream>>>(
           s.Adata, s.Bdata, s.out, nout, omap, kmap, (int)K);
-    else
+      break;
+    case TN_GK_SMALLK:
       k_einsum_smallk<false><<<blocks, 256, 0, s.stream>>>(
           s.Adata, s.Bdata, s.out, nout, omap, kmap, (int)K);
-  } else {
-    if (p2)
+      break;
+    case TN_GK_ANYK_P2:
       k_einsum_anyk<true><<<blocks, 256, 0, s.stream>>>(
           s.Adata, s.Bdata, s.out, nout, omap, kmap, K);
-    else
+      break;
+    default:  // TN_GK_ANYK
       k_einsum_anyk<false><<<blocks, 256, 0, s.stream>>>(
           s.Adata, s.Bdata, s.out, nout, omap, kmap, K);
+      break;
   }
   HIP_CHECK(hipGetLastError());
   return TN_OK;
@@ -2144,12 +2080,9 @@ static int einsum_batched_impl(const u64* out_labels, const u64* out_shape,
   };
   if (bp.cls == TN_BATCH_NONE) return element(0);
   if (bp.cls == TN_BATCH_GATHER) {
-    std::vector<AxisInfo> lead;
-    for (int x = 0; x < bp.nb; ++x)
-      lead.push_back({bp.bdim[x], A.strides[bp.ba[x]], B.strides[bp.bb[x]]});
     const Step<CT> s{e, eshape, end, bp.Ae, bp.Be, (const CT*)A.data,
                      (const CT*)B.data, out, stream, ws, stats};
-    return run_gather(s, lead);
+    return run_gather(s, batch_lead_axis_info(bp, A, B));
   }
   if (bp.cls == TN_BATCH_GEMM) {
     int rc = run_batch_gemm(bp, out_shape, out_nd, A, B, out, stream, ws,

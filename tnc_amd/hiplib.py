@@ -178,6 +178,7 @@ class StepPlan(ctypes.Structure):
         ("perm_a", ctypes.c_int32), ("perm_b", ctypes.c_int32),
         ("perm_out", ctypes.c_int32),
         ("pipe_perm_a", ctypes.c_int32), ("pipe_perm_b", ctypes.c_int32),
+        ("gather_kernel", ctypes.c_int32), ("gather_blocks", ctypes.c_int32),
     ]
 
 
@@ -186,6 +187,10 @@ DOT_LINEAR, DOT_TILED, DOT_GATHER = 0, 1, 2
 (GEMM_V1, GEMM_MFMA, GEMM_C128_GLDS, GEMM_C128_PURE, GEMM_C128_3M,
  GEMM_C128_GATHER, GEMM_C64_PURE) = range(7)
 PERM_NONE, PERM_CT, PERM_TILE = 0, 1, 2  # perm_* / pipe_perm_* fields
+# gather_kernel: k_einsum_smallk<false> / <true> / _tbl, k_einsum_anyk<false>
+# / <true>
+(GK_NONE, GK_SMALLK, GK_SMALLK_P2, GK_SMALLK_TBL, GK_ANYK,
+ GK_ANYK_P2) = range(6)
 
 
 def plan_step(out_labels, out_shape, a_labels, a_shape, b_labels, b_shape,
@@ -215,6 +220,7 @@ class BatchPlan(ctypes.Structure):
         ("dispatches", ctypes.c_uint64),
         ("ws_pack_a", ctypes.c_uint64), ("ws_pack_b", ctypes.c_uint64),
         ("elem", StepPlan),
+        ("gather_kernel", ctypes.c_int32),
     ]
 
 
