@@ -405,6 +405,63 @@ int tn_net_result_data(tn_net* net, void* host_out);
 /* Device pointer of the final tensor (valid until the next contract call). */
 void* tn_net_result_dev(tn_net* net);
 
+/* ------------------- sampling a tensor's |amplitude|^2 ------------------ */
+
+/* Draw flat indices of a contiguous complex tensor T[n] with probability
+ * |T[i]|^2 / sum |T|^2, from uniforms the caller supplies (0 <= u < 1; the
+ * library owns no random generator). Fixed semantics (DESIGN.md "Sampling
+ * the final tensor"): p[i] = re^2 + im^2 in f64; chunks of 4096 elements;
+ * S[j] the sum of p over chunk j; C the inclusive prefix of S, added one
+ * after another in ascending j; total = C[last]; t = u * total. The chunk is
+ * the first j with C[j] > t, else the last chunk that added mass; the element
+ * is the first of the chunk whose running sum exceeds t - C[j-1], else the
+ * chunk's last element with p > 0. No atomics: two runs give the same bits.
+ * An element with p == 0 is never drawn. */
+typedef struct tn_sample_plan {
+  uint64_t chunk;      /* elements per chunk (4096) */
+  uint64_t nchunks;
+  uint64_t grid_sums;  /* blocks of k_prob_chunk_sums: one per chunk */
+  uint64_t grid_scan;  /* blocks of k_prob_scan: 1 */
+  uint64_t grid_draw;  /* blocks of k_sample_draw: one per shot (0: no launch) */
+  /* workspace of tn_net_sample: nchunks doubles (C), nshots doubles (u),
+   * nshots uint64 (idx), one double (total). tn_sample_*_dev use only the
+   * first nchunks doubles. */
+  uint64_t ws_bytes;
+} tn_sample_plan;
+
+/* Plan the three launches. dtype 0 = complex128, 1 = complex64. Returns
+ * TN_ERR_INVALID for n == 0 and for more chunks or shots than one grid holds
+ * (2^31 - 1). Needs no GPU. */
+int tn_plan_sample(uint64_t n, uint64_t nshots, int dtype,
+                   tn_sample_plan* out);
+
+/* Sample a device tensor: data (n elements, contiguous, 16-byte aligned),
+ * u_dev[nshots], idx_dev[nshots], norm2_dev[1] and ws_dev are device
+ * pointers; ws_bytes must cover nchunks doubles (tn_plan_sample's ws_bytes
+ * always does). Launches on `stream` and returns without waiting; *norm2_dev
+ * receives total, which the caller checks: where it is zero or not finite
+ * the indices mean nothing (they stay inside [0, n)). u outside [0, 1) is not
+ * detected here. nshots == 0 computes total only. */
+int tn_sample_c128_dev(const void* data, uint64_t n, const double* u_dev,
+                       uint64_t nshots, uint64_t* idx_dev, double* norm2_dev,
+                       void* ws_dev, uint64_t ws_bytes, void* stream);
+int tn_sample_c64_dev(const void* data, uint64_t n, const double* u_dev,
+                      uint64_t nshots, uint64_t* idx_dev, double* norm2_dev,
+                      void* ws_dev, uint64_t ws_bytes, void* stream);
+
+/* Sample the net's final tensor (after any tn_net_contract* call), in its
+ * stored order (tn_net_result_meta). Host arrays in and out, synchronous.
+ * idx_host[s] is the flat index drawn for u_host[s]; *norm2 (optional) gets
+ * total. Workspace comes from the net's arena when there is one, else from
+ * hipMalloc, and is released before the call returns: the arena stands as it
+ * did and a captured graph of tn_net_contract stays valid. Returns
+ * TN_ERR_INVALID with nothing launched when there is no final tensor, it has
+ * no elements, or a u is outside [0, 1); after the first two launches, when
+ * total is zero ("final tensor has zero norm") or not finite ("final tensor
+ * norm is not finite"). nshots == 0 gives *norm2 only. */
+int tn_net_sample(tn_net* net, const double* u_host, uint64_t nshots,
+                  uint64_t* idx_host, double* norm2);
+
 /* Import an external DEVICE tensor (e.g. an RCCL-received intermediate) as a
  * new leaf without copying; the buffer must outlive the net or be detached
  * before reuse. */

@@ -1515,4 +1515,122 @@ inline void plan_batch_walk(bool c128, const std::vector<LayoutTensor>& leaves,
   bw->valid = true;
 }
 
+// ---- sampling the final tensor (tn_sample_*_dev, tn_net_sample) ------------
+//
+// p[i] = re^2 + im^2 in f64 (two products, one add, no fused multiply-add).
+// S[j] is the sum of p over chunk j, C the inclusive prefix of S added one
+// after another in ascending j, total = C[last]. A shot with uniform u draws
+// t = u * total, the chunk sample_pick_chunk names, and in it the element
+// sample_pick_in_chunk names for t - C[j-1]. The kernels restate the two pick
+// functions; sample_plan_check runs them on the host.
+
+#define TN_SAMPLE_CHUNK 4096   // elements per chunk: one block of pass 1
+#define TN_SAMPLE_THREADS 256  // block size of all three kernels
+#define TN_SAMPLE_SLAB 16      // consecutive elements one draw thread scans
+#define TN_SAMPLE_SCAN_TILE 2048  // entries k_prob_scan holds in LDS per pass
+
+static_assert(TN_SAMPLE_THREADS * TN_SAMPLE_SLAB == TN_SAMPLE_CHUNK,
+              "one draw block covers one chunk");
+
+struct SamplePlan {
+  bool valid = false;
+  std::string err;
+  u64 chunk = TN_SAMPLE_CHUNK;
+  u64 nchunks = 0;
+  u64 grid_sums = 0;  // k_prob_chunk_sums: one block per chunk
+  u64 grid_scan = 0;  // k_prob_scan: one block
+  u64 grid_draw = 0;  // k_sample_draw: one block per shot; 0 = not launched
+  // C[nchunks] | u[nshots] | idx[nshots] | total, in this order. The *_dev
+  // entry points use the C part only (off_u bytes).
+  u64 off_u = 0, off_idx = 0, off_total = 0, ws_bytes = 0;
+};
+
+inline void plan_sample(u64 n, u64 nshots, u64 esize, SamplePlan* sp) {
+  *sp = SamplePlan();
+  if (esize != 16 && esize != 8) {
+    sp->err = "dtype must be 0 (c128) or 1 (c64)";
+    return;
+  }
+  if (n == 0) {
+    sp->err = "tensor has no elements";
+    return;
+  }
+  if (n > ~(u64)0 / esize) {
+    sp->err = "tensor size overflows 64 bits";
+    return;
+  }
+  sp->nchunks = (n - 1) / TN_SAMPLE_CHUNK + 1;
+  // a grid is at most 2^31 - 1 blocks
+  if (sp->nchunks > 0x7fffffffull || nshots > 0x7fffffffull) {
+    sp->err = "more chunks or shots than one grid holds";
+    return;
+  }
+  sp->grid_sums = sp->nchunks;
+  sp->grid_scan = 1;
+  sp->grid_draw = nshots;
+  sp->off_u = sp->nchunks * 8;
+  sp->off_idx = sp->off_u + nshots * 8;
+  sp->off_total = sp->off_idx + nshots * 8;
+  sp->ws_bytes = sp->off_total + 8;
+  sp->valid = true;
+}
+
+// The chunk of a shot: the first j with C[j] > t; where there is none
+// (rounding of u * total at u next to 1) the last chunk that added mass, the
+// last j with C[j] > C[j-1], C[-1] = 0. C is non-decreasing, so both are
+// bisections: the last chunk that added mass is the first whose C reaches
+// C[last]. 0 when no chunk added mass (total == 0, refused before any draw).
+// A chunk whose S is positive but is lost in the rounding of C[j-1] + S[j]
+// counts as having added none.
+inline u64 sample_pick_chunk(const double* C, u64 nchunks, double t) {
+  u64 lo = 0, hi = nchunks;  // C[x] <= t for x < lo, C[x] > t for x >= hi
+  while (lo < hi) {
+    const u64 mid = lo + (hi - lo) / 2;
+    if (C[mid] > t)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  if (lo < nchunks) return lo;
+  const double top = C[nchunks - 1];
+  lo = 0, hi = nchunks - 1;  // C[x] < top for x < lo, C[hi] reaches top
+  while (lo < hi) {
+    const u64 mid = lo + (hi - lo) / 2;
+    if (C[mid] < top)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// The element of a shot inside its chunk: the first i with p[i] > 0 and
+// r > t, r the running sum in element order, taken slab by slab as
+// k_sample_draw takes it:
+// the sum of each slab of TN_SAMPLE_SLAB elements starts from zero, the slab
+// sums in front of a slab are added one after another in ascending order, and
+// the slab's own elements are added to that in order. Where the p are exactly
+// representable sums this is the plain left-to-right sum, under which p > 0
+// holds of itself at the first r > t; with slabs a slab's offset may round
+// past t where no r in front of it did, and the test on p keeps an element
+// without mass from being drawn there. Where no element qualifies, the last
+// with p > 0; 0 for a chunk without mass, which sample_pick_chunk never
+// names. NaN compares false everywhere and ends in the same clamp.
+inline u64 sample_pick_in_chunk(const double* p, u64 len, double t) {
+  double off = 0.0;
+  for (u64 base = 0; base < len; base += TN_SAMPLE_SLAB) {
+    const u64 end = std::min<u64>(base + TN_SAMPLE_SLAB, len);
+    double r = off, slab = 0.0;
+    for (u64 i = base; i < end; ++i) {
+      r += p[i];
+      if (p[i] > 0.0 && r > t) return i;
+      slab += p[i];
+    }
+    off += slab;
+  }
+  for (u64 i = len; i-- > 0;)
+    if (p[i] > 0.0) return i;
+  return 0;
+}
+
 #endif  // TNC_STEP_PLAN_HPP

@@ -3643,3 +3643,402 @@ extern "C" void tn_net_destroy(tn_net* net) {
   if (net->stream2) (void)hipStreamDestroy(net->stream2);
   delete net;
 }
+
+// ---------------------------------------------------------------------------
+// sampling: flat indices of a contiguous complex tensor drawn with
+// probability |T[i]|^2 (semantics: include/tnc_hip.h, step_plan.hpp). Three
+// launches: chunk sums (the one pass over the tensor, HBM-bound), their
+// sequential prefix in one block, one block per shot that bisects the prefix
+// and scans one chunk out of LDS.
+// ---------------------------------------------------------------------------
+
+// p = re^2 + im^2 in f64: two products and one add, never a fused
+// multiply-add, so pass 1, the draw and a host reference round alike
+template <typename RT>
+__device__ __forceinline__ double sample_prob(RT re, RT im) {
+#pragma clang fp contract(off)
+  const double a = (double)re * (double)re;
+  const double b = (double)im * (double)im;
+  return a + b;
+}
+
+// p of element e of a full chunk lands in v[]: 16-byte loads, lane-contiguous.
+// c128: load it holds element it*256+tid. c64: load it holds elements
+// 2*(it*256+tid) and the one after it.
+template <typename CT>
+struct SampleLoad;
+
+template <>
+struct SampleLoad<double2> {
+  static constexpr int LOADS = TN_SAMPLE_CHUNK / TN_SAMPLE_THREADS;
+  static constexpr int PER = 1;
+  typedef double2 Vec;
+  static __device__ __forceinline__ void probs(const Vec& v, double* p) {
+    p[0] = sample_prob(v.x, v.y);
+  }
+};
+
+template <>
+struct SampleLoad<float2> {
+  static constexpr int LOADS = TN_SAMPLE_CHUNK / TN_SAMPLE_THREADS / 2;
+  static constexpr int PER = 2;
+  typedef float4 Vec;
+  static __device__ __forceinline__ void probs(const Vec& v, double* p) {
+    p[0] = sample_prob(v.x, v.y);
+    p[1] = sample_prob(v.z, v.w);
+  }
+};
+
+// S[j] = sum of p over chunk j = blockIdx.x. Fixed order: each lane adds its
+// loads in load order, lanes are added by xor-shuffles, waves one after
+// another. A short last chunk goes element by element.
+template <typename CT>
+__global__ __launch_bounds__(TN_SAMPLE_THREADS) void k_prob_chunk_sums(
+    const CT* __restrict__ T, double* __restrict__ S, u64 n) {
+  typedef SampleLoad<CT> LD;
+  __shared__ double sred[TN_SAMPLE_THREADS / 64];
+  const int tid = threadIdx.x;
+  const u64 base = (u64)blockIdx.x * TN_SAMPLE_CHUNK;
+  const u64 len = n - base < TN_SAMPLE_CHUNK ? n - base : TN_SAMPLE_CHUNK;
+  const CT* src = T + base;
+  double acc = 0.0;
+  if (len == TN_SAMPLE_CHUNK) {
+    const typename LD::Vec* srcv =
+        reinterpret_cast<const typename LD::Vec*>(src);
+    typename LD::Vec v[LD::LOADS];
+#pragma unroll
+    for (int it = 0; it < LD::LOADS; ++it)
+      v[it] = srcv[it * TN_SAMPLE_THREADS + tid];
+#pragma unroll
+    for (int it = 0; it < LD::LOADS; ++it) {
+      double p[LD::PER];
+      LD::probs(v[it], p);
+#pragma unroll
+      for (int x = 0; x < LD::PER; ++x) acc += p[x];
+    }
+  } else {
+    for (u64 e = tid; e < len; e += TN_SAMPLE_THREADS) {
+      const CT v = src[e];
+      acc += sample_prob(v.x, v.y);
+    }
+  }
+  for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
+  if ((tid & 63) == 0) sred[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double tot = sred[0];
+    for (int w = 1; w < TN_SAMPLE_THREADS / 64; ++w) tot += sred[w];
+    S[blockIdx.x] = tot;
+  }
+}
+
+// C[j] = C[j-1] + S[j] in place, one add after another in ascending j: the
+// association is part of the semantics, so one thread adds. The block only
+// moves the entries through LDS, TILE per pass. (A template, so that it is
+// placed in the code object where it is first used, behind the kernels that
+// were there before it.)
+template <int TILE>
+__global__ __launch_bounds__(TN_SAMPLE_THREADS) void k_prob_scan(
+    double* __restrict__ SC, u64 nchunks, double* __restrict__ total) {
+  constexpr int B = 16;  // entries thread 0 holds in registers at a time
+  constexpr int PER = TILE / TN_SAMPLE_THREADS;  // entries a thread moves
+  static_assert(TILE % B == 0 && TILE % TN_SAMPLE_THREADS == 0, "whole");
+  __shared__ double tile[TILE];
+  const int tid = threadIdx.x;
+  // One block hides no latency behind other blocks: a thread's entries of
+  // the next tile are loaded into v[] while thread 0 adds up this one.
+  // Entries past the end are zeros: adding them leaves run as it is.
+  double v[PER];
+  auto load = [&](u64 base) {
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const u64 e = base + (u64)(k * TN_SAMPLE_THREADS + tid);
+      v[k] = e < nchunks ? SC[e] : 0.0;
+    }
+  };
+  load(0);
+  double run = 0.0;  // thread 0's
+  for (u64 base = 0; base < nchunks; base += TILE) {
+    const int len = nchunks - base < TILE ? (int)(nchunks - base) : TILE;
+    const int padded = (len + B - 1) / B * B;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) tile[k * TN_SAMPLE_THREADS + tid] = v[k];
+    __syncthreads();
+    if (base + TILE < nchunks) load(base + TILE);
+    if (tid == 0) {
+      // the adds are one dependent chain; the LDS reads of the next batch
+      // are issued ahead of it so that only the adds are waited for
+      double cur[B], nxt[B];
+#pragma unroll
+      for (int i = 0; i < B; ++i) cur[i] = tile[i];
+      for (int b = 0; b < padded; b += B) {
+        if (b + B < padded) {
+#pragma unroll
+          for (int i = 0; i < B; ++i) nxt[i] = tile[b + B + i];
+        }
+#pragma unroll
+        for (int i = 0; i < B; ++i) {
+          run += cur[i];
+          tile[b + i] = run;
+        }
+#pragma unroll
+        for (int i = 0; i < B; ++i) cur[i] = nxt[i];
+      }
+    }
+    __syncthreads();
+    // each thread stores the entries it wrote and will overwrite next pass
+    for (int e = tid; e < len; e += TN_SAMPLE_THREADS) SC[base + e] = tile[e];
+  }
+  if (tid == 0) *total = run;
+}
+
+// One shot per block: restates sample_pick_chunk and sample_pick_in_chunk
+// (step_plan.hpp). The chunk's p values go to LDS with one pad double per
+// slab, so that the per-thread slab reads spread over the banks.
+template <typename CT>
+__global__ __launch_bounds__(TN_SAMPLE_THREADS) void k_sample_draw(
+    const CT* __restrict__ T, u64 n, const double* __restrict__ C,
+    u64 nchunks, const double* __restrict__ total,
+    const double* __restrict__ u, u64* __restrict__ idx) {
+  typedef SampleLoad<CT> LD;
+  constexpr int STRIDE = TN_SAMPLE_SLAB + 1;
+  __shared__ double sp[TN_SAMPLE_THREADS * STRIDE];
+  __shared__ double sslab[TN_SAMPLE_THREADS];
+  __shared__ int sfirst[TN_SAMPLE_THREADS / 64], slast[TN_SAMPLE_THREADS / 64];
+  const int tid = threadIdx.x;
+  const double t = u[blockIdx.x] * *total;
+
+  // sample_pick_chunk, the same in every thread
+  u64 lo = 0, hi = nchunks;
+  while (lo < hi) {
+    const u64 mid = lo + (hi - lo) / 2;
+    if (C[mid] > t)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  if (lo == nchunks) {
+    const double top = C[nchunks - 1];
+    lo = 0, hi = nchunks - 1;
+    while (lo < hi) {
+      const u64 mid = lo + (hi - lo) / 2;
+      if (C[mid] < top)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+  }
+  const u64 j = lo;
+  const double tp = t - (j ? C[j - 1] : 0.0);
+
+  // the chunk's p, zero past the end of a short last chunk
+  const u64 base = j * TN_SAMPLE_CHUNK;
+  const u64 len = n - base < TN_SAMPLE_CHUNK ? n - base : TN_SAMPLE_CHUNK;
+  const CT* src = T + base;
+  if (len == TN_SAMPLE_CHUNK) {
+    const typename LD::Vec* srcv =
+        reinterpret_cast<const typename LD::Vec*>(src);
+    typename LD::Vec v[LD::LOADS];
+#pragma unroll
+    for (int it = 0; it < LD::LOADS; ++it)
+      v[it] = srcv[it * TN_SAMPLE_THREADS + tid];
+#pragma unroll
+    for (int it = 0; it < LD::LOADS; ++it) {
+      double p[LD::PER];
+      LD::probs(v[it], p);
+#pragma unroll
+      for (int x = 0; x < LD::PER; ++x) {
+        const int e = (it * TN_SAMPLE_THREADS + tid) * LD::PER + x;
+        sp[e + e / TN_SAMPLE_SLAB] = p[x];
+      }
+    }
+  } else {
+    for (int e = tid; e < TN_SAMPLE_CHUNK; e += TN_SAMPLE_THREADS) {
+      double p = 0.0;
+      if ((u64)e < len) {
+        const CT v = src[e];
+        p = sample_prob(v.x, v.y);
+      }
+      sp[e + e / TN_SAMPLE_SLAB] = p;
+    }
+  }
+  __syncthreads();
+
+  // sample_pick_in_chunk: own slab from zero, the slab sums in front added
+  // one after another, then the slab's elements added to that in order
+  double v[TN_SAMPLE_SLAB];
+  double slab = 0.0;
+#pragma unroll
+  for (int i = 0; i < TN_SAMPLE_SLAB; ++i) {
+    v[i] = sp[tid * STRIDE + i];
+    slab += v[i];
+  }
+  sslab[tid] = slab;
+  __syncthreads();
+  double r = 0.0;
+  for (int k = 0; k < tid; ++k) r += sslab[k];
+  int first = TN_SAMPLE_CHUNK, last = -1;
+#pragma unroll
+  for (int i = 0; i < TN_SAMPLE_SLAB; ++i) {
+    r += v[i];
+    if (v[i] > 0.0) {
+      last = tid * TN_SAMPLE_SLAB + i;
+      if (first == TN_SAMPLE_CHUNK && r > tp) first = last;
+    }
+  }
+  for (int s = 32; s > 0; s >>= 1) {
+    first = min(first, __shfl_xor(first, s, 64));
+    last = max(last, __shfl_xor(last, s, 64));
+  }
+  if ((tid & 63) == 0) {
+    sfirst[tid >> 6] = first;
+    slast[tid >> 6] = last;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < TN_SAMPLE_THREADS / 64; ++w) {
+      first = min(first, sfirst[w]);
+      last = max(last, slast[w]);
+    }
+    const int i = first < TN_SAMPLE_CHUNK ? first : (last >= 0 ? last : 0);
+    idx[blockIdx.x] = base + (u64)i;
+  }
+}
+
+extern "C" int tn_plan_sample(u64 n, u64 nshots, int dtype,
+                              tn_sample_plan* out) {
+  if (dtype != 0 && dtype != 1)
+    FAILV(TN_ERR_INVALID, "dtype must be 0 (c128) or 1 (c64)");
+  if (!out) FAILV(TN_ERR_INVALID, "null plan");
+  SamplePlan sp;
+  plan_sample(n, nshots, dtype == 0 ? 16 : 8, &sp);
+  if (!sp.valid) FAILV(TN_ERR_INVALID, "%s", sp.err.c_str());
+  out->chunk = sp.chunk;
+  out->nchunks = sp.nchunks;
+  out->grid_sums = sp.grid_sums;
+  out->grid_scan = sp.grid_scan;
+  out->grid_draw = sp.grid_draw;
+  out->ws_bytes = sp.ws_bytes;
+  return TN_OK;
+}
+
+// passes 1 and 2: C[nchunks] and *total
+template <typename CT>
+static int sample_launch_sums(const SamplePlan& sp, const void* data, u64 n,
+                              double* C, double* total, hipStream_t stream) {
+  k_prob_chunk_sums<CT><<<dim3((unsigned)sp.grid_sums), TN_SAMPLE_THREADS, 0,
+                          stream>>>((const CT*)data, C, n);
+  k_prob_scan<TN_SAMPLE_SCAN_TILE><<<dim3((unsigned)sp.grid_scan),
+                                     TN_SAMPLE_THREADS, 0, stream>>>(
+      C, sp.nchunks, total);
+  HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+template <typename CT>
+static int sample_launch_draw(const SamplePlan& sp, const void* data, u64 n,
+                              const double* C, const double* total,
+                              const double* u, u64* idx, hipStream_t stream) {
+  if (!sp.grid_draw) return TN_OK;
+  k_sample_draw<CT><<<dim3((unsigned)sp.grid_draw), TN_SAMPLE_THREADS, 0,
+                      stream>>>((const CT*)data, n, C, sp.nchunks, total, u,
+                                idx);
+  HIP_CHECK(hipGetLastError());
+  return TN_OK;
+}
+
+template <typename CT>
+static int sample_dev_impl(const void* data, u64 n, const double* u_dev,
+                           u64 nshots, u64* idx_dev, double* norm2_dev,
+                           void* ws_dev, u64 ws_bytes, void* stream) {
+  SamplePlan sp;
+  plan_sample(n, nshots, sizeof(CT), &sp);
+  if (!sp.valid) FAILV(TN_ERR_INVALID, "%s", sp.err.c_str());
+  if (!data || !norm2_dev || !ws_dev || (nshots && (!u_dev || !idx_dev)))
+    FAILV(TN_ERR_INVALID, "null pointer");
+  if ((uintptr_t)data % 16 || (uintptr_t)ws_dev % 8)
+    FAILV(TN_ERR_INVALID,
+          "data must be 16-byte aligned and the workspace 8-byte aligned");
+  if (ws_bytes < sp.off_u)
+    FAILV(TN_ERR_INVALID, "workspace of %llu bytes, %llu needed",
+          (unsigned long long)ws_bytes, (unsigned long long)sp.off_u);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = sample_launch_sums<CT>(sp, data, n, (double*)ws_dev, norm2_dev,
+                                      s))
+    return rc;
+  return sample_launch_draw<CT>(sp, data, n, (const double*)ws_dev, norm2_dev,
+                                u_dev, idx_dev, s);
+}
+
+extern "C" int tn_sample_c128_dev(const void* data, u64 n,
+                                  const double* u_dev, u64 nshots,
+                                  u64* idx_dev, double* norm2_dev,
+                                  void* ws_dev, u64 ws_bytes, void* stream) {
+  return sample_dev_impl<double2>(data, n, u_dev, nshots, idx_dev, norm2_dev,
+                                  ws_dev, ws_bytes, stream);
+}
+
+extern "C" int tn_sample_c64_dev(const void* data, u64 n, const double* u_dev,
+                                 u64 nshots, u64* idx_dev, double* norm2_dev,
+                                 void* ws_dev, u64 ws_bytes, void* stream) {
+  return sample_dev_impl<float2>(data, n, u_dev, nshots, idx_dev, norm2_dev,
+                                 ws_dev, ws_bytes, stream);
+}
+
+extern "C" int tn_net_sample(tn_net* net, const double* u_host, u64 nshots,
+                             u64* idx_host, double* norm2) {
+  if (!net || !net->has_final || !net->final_t.data)
+    FAILV(TN_ERR_INVALID, "no final tensor to sample: contract first");
+  const u64 n = net->final_t.elems;
+  if (n == 0) FAILV(TN_ERR_INVALID, "final tensor has no elements");
+  if (nshots && (!u_host || !idx_host))
+    FAILV(TN_ERR_INVALID, "null pointer");
+  for (u64 s = 0; s < nshots; ++s)
+    if (!(u_host[s] >= 0.0 && u_host[s] < 1.0))
+      FAILV(TN_ERR_INVALID, "u[%llu] = %.17g is outside [0, 1)",
+            (unsigned long long)s, u_host[s]);
+  SamplePlan sp;
+  plan_sample(n, nshots, net->esize, &sp);
+  if (!sp.valid) FAILV(TN_ERR_INVALID, "%s", sp.err.c_str());
+  HIP_CHECK(hipSetDevice(net->device));
+  // one block, from the arena when there is one, never from the
+  // stream-ordered pool (ws_alloc); released on every way out of here
+  WsCtx ws{net->arena.base ? &net->arena : nullptr, net->stream};
+  WsBlock<char> blk(ws);
+  if (int rc = blk.alloc(sp.ws_bytes)) return rc;
+  double* C = (double*)blk.p;
+  double* u_dev = (double*)(blk.p + sp.off_u);
+  u64* idx_dev = (u64*)(blk.p + sp.off_idx);
+  double* total_dev = (double*)(blk.p + sp.off_total);
+  const void* data = net->final_t.data;
+  const bool c128 = net->dtype == 0;
+  int rc = c128 ? sample_launch_sums<double2>(sp, data, n, C, total_dev,
+                                              net->stream)
+                : sample_launch_sums<float2>(sp, data, n, C, total_dev,
+                                             net->stream);
+  if (rc) {
+    (void)hipStreamSynchronize(net->stream);
+    return rc;
+  }
+  // the block goes back to the arena only once nothing in flight uses it
+  hipError_t err = hipStreamSynchronize(net->stream);
+  double total = 0.0;
+  if (err == hipSuccess)
+    err = hipMemcpy(&total, total_dev, sizeof total, hipMemcpyDeviceToHost);
+  HIP_CHECK(err);
+  if (norm2) *norm2 = total;
+  if (total == 0.0) FAILV(TN_ERR_INVALID, "final tensor has zero norm");
+  if (!(total - total == 0.0))
+    FAILV(TN_ERR_INVALID, "final tensor norm is not finite");
+  if (!nshots) return TN_OK;
+  HIP_CHECK(hipMemcpy(u_dev, u_host, nshots * 8, hipMemcpyHostToDevice));
+  rc = c128 ? sample_launch_draw<double2>(sp, data, n, C, total_dev, u_dev,
+                                          idx_dev, net->stream)
+            : sample_launch_draw<float2>(sp, data, n, C, total_dev, u_dev,
+                                         idx_dev, net->stream);
+  err = hipStreamSynchronize(net->stream);
+  if (rc) return rc;
+  HIP_CHECK(err);
+  HIP_CHECK(hipMemcpy(idx_host, idx_dev, nshots * 8, hipMemcpyDeviceToHost));
+  return TN_OK;
+}

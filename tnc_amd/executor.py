@@ -257,6 +257,9 @@ class ContractionEngine:
             if idx < 0:
                 raise RuntimeError(f"tn_net_add_leaf failed: {hiplib.last_error()}")
         self._pairs = hiplib._u64arr([x for p in steps for x in p])
+        # sum of |amplitude|^2 over the final tensor, as the last sample() or
+        # sample_flat() measured it
+        self.sample_norm2 = None
 
     def _refuse_batched(self, what):
         if self.batch_edges is not None:
@@ -333,17 +336,23 @@ class ContractionEngine:
         )
         return ms.value, list(step_ms), list(gemm_ms), list(kind)
 
-    def result(self) -> "tuple[list, np.ndarray]":
-        L = hiplib.lib()
+    def _result_meta(self):
+        """(legs, dims) of the final tensor in stored order."""
         labels = (ctypes.c_uint64 * 64)()
         dims = (ctypes.c_uint64 * 64)()
         nd = ctypes.c_size_t()
         hiplib.check(
-            L.tn_net_result_meta(self.net, labels, dims, ctypes.byref(nd)),
+            hiplib.lib().tn_net_result_meta(self.net, labels, dims,
+                                            ctypes.byref(nd)),
             "tn_net_result_meta",
         )
-        shape = tuple(dims[i] for i in range(nd.value))
-        legs = [labels[i] for i in range(nd.value)]
+        return ([labels[i] for i in range(nd.value)],
+                [dims[i] for i in range(nd.value)])
+
+    def result(self) -> "tuple[list, np.ndarray]":
+        L = hiplib.lib()
+        legs, dims = self._result_meta()
+        shape = tuple(dims)
         out = np.empty(shape, dtype=self.npdtype)
         hiplib.check(
             L.tn_net_result_data(self.net, out.ctypes.data_as(ctypes.c_void_p)),
@@ -357,6 +366,31 @@ class ContractionEngine:
         if not ptr:
             raise RuntimeError("no result available")
         return ptr
+
+    def sample_flat(self, u) -> np.ndarray:
+        """Flat indices into the final tensor (stored order), one per
+        uniform of u (each 0 <= u < 1), drawn on the device with probability
+        |amplitude|^2 (tn_net_sample); the tensor stays where it is. Sets
+        sample_norm2. An empty u measures the norm only."""
+        u = np.ascontiguousarray(u, dtype=np.float64).ravel()
+        idx = np.empty(u.size, dtype=np.uint64)
+        norm2 = ctypes.c_double(float("nan"))
+        rc = hiplib.lib().tn_net_sample(
+            self.net, u.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            u.size, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            ctypes.byref(norm2))
+        hiplib.check(rc, "tn_net_sample")
+        self.sample_norm2 = norm2.value
+        return idx
+
+    def sample(self, u) -> "tuple[list, np.ndarray]":
+        """Shots from the final tensor of the last contract(),
+        contract_batched() or contract_sliced(). Returns (legs, digits):
+        the legs in stored order and digits[nshots, rank], the value drawn
+        on every leg for every uniform of u."""
+        idx = self.sample_flat(u)
+        legs, dims = self._result_meta()
+        return legs, decode_digits(idx, dims)
 
     def close(self):
         if getattr(self, "net", None):
@@ -403,3 +437,93 @@ def amplitudes_gpu(tn: CompositeTensor, replace_path, batch_edge, device=0,
         legs = [legs[x] for x in order]
         data = np.ascontiguousarray(np.transpose(data, order))
     return legs, data
+
+
+def decode_digits(idx, dims) -> np.ndarray:
+    """The mixed-radix digits of flat row-major indices over dims, last dim
+    fastest: an int64 array [len(idx), len(dims)]. Pure numpy."""
+    rest = np.asarray(idx).astype(np.int64).ravel()
+    digits = np.empty((rest.size, len(dims)), dtype=np.int64)
+    for x in range(len(dims) - 1, -1, -1):
+        digits[:, x] = rest % int(dims[x])
+        rest = rest // int(dims[x])
+    if rest.size and np.any(rest):
+        raise ValueError("index beyond the tensor")
+    return digits
+
+
+def decode_bitstrings(legs, digits, target_leg_order, batch_edge=None,
+                      bitstrings=None):
+    """One string per shot, in qubit order, from the digits drawn on the
+    legs of a final tensor (ContractionEngine.sample). target_leg_order is
+    the Permutor's: the open edges in qubit order. Without `bitstrings` a
+    string holds the open qubits only. With it, the strings given to
+    into_amplitudes_network (or the one given to into_amplitude_network), a
+    string is the drawn row of `bitstrings`, the digit on batch_edge (row 0
+    where no leg is batch_edge), with every '*' replaced by that qubit's
+    drawn bit. Pure numpy."""
+    legs = list(legs)
+    digits = np.asarray(digits)
+    if digits.ndim != 2 or digits.shape[1] != len(legs):
+        raise ValueError("digits must be [nshots, len(legs)]")
+    column = {l: x for x, l in enumerate(legs)}
+    known = set(target_leg_order) | {batch_edge}
+    if len(column) != len(legs) or not set(legs) <= known:
+        raise ValueError("a leg is neither an open edge nor the batch edge")
+    try:
+        open_cols = [column[e] for e in target_leg_order]
+    except KeyError as e:
+        raise ValueError(f"open edge {e} is no leg of the tensor") from None
+    if batch_edge in column:
+        rows = digits[:, column[batch_edge]]
+    else:
+        rows = np.zeros(digits.shape[0], dtype=np.int64)
+    if bitstrings is not None:
+        bitstrings = list(bitstrings)
+        for b in bitstrings:
+            if b.count("*") != len(open_cols):
+                raise ValueError("bitstrings must have one '*' per open edge")
+        if rows.size and int(rows.max()) >= len(bitstrings):
+            raise ValueError("drawn row beyond the bitstrings given")
+    out = []
+    for s in range(digits.shape[0]):
+        bits = [str(int(d)) for d in digits[s, open_cols]]
+        if bitstrings is None:
+            out.append("".join(bits))
+            continue
+        it = iter(bits)
+        out.append("".join(next(it) if c == "*" else c
+                           for c in bitstrings[int(rows[s])]))
+    return out
+
+
+def sample_bitstrings_gpu(tn: CompositeTensor, replace_path, permutor, shots,
+                          seed=0, device=0, dtype="c128", batch_edge=None,
+                          bitstrings=None):
+    """`shots` bitstrings drawn from a circuit network with probability
+    |amplitude|^2: one contraction (batched when the network carries
+    batch_edge), then the shots are drawn on the device from the final
+    tensor, with uniforms from numpy.random.default_rng(seed). tn, permutor
+    (and batch_edge, bitstrings) as Circuit.into_statevector_network,
+    into_amplitude_network or into_amplitudes_network return and take them.
+    Strings are as decode_bitstrings builds them. With several bitstrings the
+    draw is over the whole [B, open...] block: a row with more mass in its
+    open qubits is drawn more often."""
+    u = np.random.default_rng(seed).random(int(shots))
+    batch_edges = None
+    if batch_edge is not None:
+        carried = any(batch_edge in t.legs
+                      for t in flatten_network(tn, replace_path)[0])
+        batch_edges = [batch_edge] if carried else []
+    eng = ContractionEngine(tn, replace_path, device, dtype,
+                            batch_edges=batch_edges)
+    try:
+        if batch_edges is None:
+            eng.contract()
+        else:
+            eng.contract_batched()
+        legs, digits = eng.sample(u)
+    finally:
+        eng.close()
+    return decode_bitstrings(legs, digits, permutor.target_leg_order,
+                             batch_edge, bitstrings)

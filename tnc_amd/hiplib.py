@@ -150,8 +150,48 @@ def lib() -> ctypes.CDLL:
             ctypes.c_void_p, u64p, ctypes.c_size_t, u64p, ctypes.c_size_t,
             ctypes.POINTER(ctypes.c_double),
         ]
+        L.tn_plan_sample.restype = ctypes.c_int
+        L.tn_plan_sample.argtypes = [
+            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+            ctypes.POINTER(SamplePlan),
+        ]
+        for name in ("tn_sample_c128_dev", "tn_sample_c64_dev"):
+            fn = getattr(L, name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [
+                ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+            ]
+        L.tn_net_sample.restype = ctypes.c_int
+        L.tn_net_sample.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_uint64,
+            u64p, ctypes.POINTER(ctypes.c_double),
+        ]
         _lib = L
     return _lib
+
+
+class SamplePlan(ctypes.Structure):
+    """tn_sample_plan (include/tnc_hip.h): the three launches of a sampling
+    call and the workspace tn_net_sample takes."""
+
+    _fields_ = [
+        ("chunk", ctypes.c_uint64), ("nchunks", ctypes.c_uint64),
+        ("grid_sums", ctypes.c_uint64), ("grid_scan", ctypes.c_uint64),
+        ("grid_draw", ctypes.c_uint64), ("ws_bytes", ctypes.c_uint64),
+    ]
+
+
+def plan_sample(n, nshots, dtype="c128") -> SamplePlan:
+    """The plan of sampling nshots indices from a tensor of n elements
+    (tn_plan_sample). Raises on a refused plan. Needs no GPU."""
+    plan = SamplePlan()
+    rc = lib().tn_plan_sample(int(n), int(nshots),
+                              {"c128": 0, "c64": 1}[dtype],
+                              ctypes.byref(plan))
+    check(rc, "tn_plan_sample")
+    return plan
 
 
 class StepPlan(ctypes.Structure):
