@@ -464,12 +464,24 @@ int tn_net_sample(tn_net* net, const double* u_host, uint64_t nshots,
 
 /* Import an external DEVICE tensor (e.g. an RCCL-received intermediate) as a
  * new leaf without copying; the buffer must outlive the net or be detached
- * before reuse. */
+ * before reuse. The contents of the buffer may change between contract calls
+ * (a receive landing in the same buffer every round): every tn_net_contract*
+ * call reads them as they are when the call is made, whether it walks
+ * normally, captures a graph or replays one, since a captured graph reads
+ * through this pointer. The pointer, the labels and the dims may not
+ * change. */
 int64_t tn_net_add_leaf_dev(tn_net* net, const uint64_t* labels,
                             const uint64_t* dims, size_t ndim, void* dev_data);
 
 /* Bytes currently held by the net's device pool (watermark telemetry). */
 int tn_net_pool_bytes(tn_net* net, uint64_t* in_use, uint64_t* cached);
+
+/* Replay telemetry: *plain gets the state of tn_net_contract's graph, *sliced
+ * that of tn_net_contract_sliced's (0 when there is no slice state):
+ * 0 nothing armed, 1 armed (the next identical call captures), 2 captured
+ * (identical calls replay), -1 disabled after a spill or failure. Either may
+ * be NULL. */
+int tn_net_replay_state(tn_net* net, int32_t* plain, int32_t* sliced);
 
 void tn_net_destroy(tn_net* net);
 

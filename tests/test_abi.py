@@ -29,6 +29,20 @@ def test_exports_match_header():
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="library not built")
+def test_replay_state_refuses_a_null_net():
+    """tn_net_replay_state on no net is TN_ERR_INVALID (1); needs no GPU."""
+    from tnc_amd import hiplib
+
+    L = hiplib.lib()
+    plain, sliced = ctypes.c_int32(7), ctypes.c_int32(7)
+    assert L.tn_net_replay_state(None, ctypes.byref(plain),
+                                 ctypes.byref(sliced)) == 1
+    assert L.tn_net_replay_state(None, None, None) == 1
+    assert "null net" in hiplib.last_error()
+    assert (plain.value, sliced.value) == (7, 7)  # nothing written
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="library not built")
 def test_no_gpu_fails_loudly():
     """Without a GPU the compute entry points must error, never fall back."""
     lib = ctypes.CDLL(LIB)

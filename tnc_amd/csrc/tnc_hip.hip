@@ -3629,6 +3629,14 @@ extern "C" int tn_net_pool_bytes(tn_net* net, u64* in_use, u64* cached) {
   return TN_OK;
 }
 
+extern "C" int tn_net_replay_state(tn_net* net, int32_t* plain,
+                                   int32_t* sliced) {
+  if (!net) FAILV(TN_ERR_INVALID, "null net");
+  if (plain) *plain = net->graph_state;
+  if (sliced) *sliced = net->slices ? net->slices->graph_state : 0;
+  return TN_OK;
+}
+
 extern "C" void tn_net_destroy(tn_net* net) {
   if (!net) return;
   (void)hipSetDevice(net->device);

@@ -94,6 +94,11 @@ def lib() -> ctypes.CDLL:
             ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
             ctypes.POINTER(ctypes.c_uint64),
         ]
+        L.tn_net_replay_state.restype = ctypes.c_int
+        L.tn_net_replay_state.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+            ctypes.POINTER(ctypes.c_int32),
+        ]
         L.tn_net_destroy.argtypes = [ctypes.c_void_p]
         L.tn_plan_step.restype = ctypes.c_int
         L.tn_plan_step.argtypes = [
